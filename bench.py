@@ -7,7 +7,13 @@ One "step" = Trainer.step on a synthetic batch held in pinned host memory: the H
 loss + backward + (all-reduce) + Adam.  The K timed steps run back to back between a barrier +
 device synchronize on both sides; per-step times are HIP events recorded on the compute
 stream at every step boundary, max over ranks, and ``value`` uses their MEDIAN (the wall time
-of the K steps is reported beside it).  Prints ONE JSON line (rank 0) with the roofline of the stem conv
+of the K steps is reported beside it).  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the line (``roofline``,
+``cpu_baseline``, ``fp32_parity_build_value`` and ``clock`` are null).  ``--dump-outputs DIR``
+also writes what the last timed step left (the loss it returned, the parameters, gradients and
+BatchNorm buffers it updated) as ``DIR/<name>.npy``.  ``--full`` adds the other legs: the
+shader clock over the timed steps and the roofline of the stem conv
 (forward + weight-gradient kernels, HBM-bound: ``frac`` on BASELINE.md's 578.9 MB at N=2,
 ``frac_fused`` on the 847.3 MB the product's kernels move with the stem's BatchNorm-backward
 apply fused into the weight gradient), their launch
@@ -49,6 +55,13 @@ def parse():
     ap.add_argument("--zero-fill", action="store_true", help="config 4: 1-2 modalities zeroed")
     ap.add_argument("--ckpt-decoder", action="store_true", help="config 5: decoder activation checkpointing")
     ap.add_argument("--fp32-steps", type=int, default=5, help="timed steps of the fp32 parity build (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the stem roofline (HIP events inside the timed steps) and the shader "
+                         "clock, the fp32 parity build (--fp32-steps) and the CPU oracle baseline "
+                         "(unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, parameters, gradients, "
+                         "BatchNorm buffers) as DIR/<name>.npy (float32; a fixed seeded sample of a large array)")
     ap.add_argument("--plumbing", action="store_true",
                     help="launcher check only (CPU, gloo): every rank joins the group, rank 0 prints the "
                          "world size it saw; no GPU work, no measurement")
@@ -334,12 +347,13 @@ def _pinned_batches(n, spatial, rank, count, zero_fill):
     return out
 
 
-def timed_steps(tr, host_batches, warmup, steps, world):
+def timed_steps(tr, host_batches, warmup, steps, world, clock=True):
     """K steps back to back, bracketed by a barrier + device synchronize on both sides (the
     host enqueues ahead of the GPU, as a training loop without per-step host syncs does).
     Per-step times come from HIP events recorded on the compute stream at every step
     boundary; returns (per-step seconds, max over ranks), the wall time of the K steps, and
-    the last loss, and the shader clock over the K steps (ClockProbe.summary, this rank)."""
+    the last loss, and the shader clock over the K steps (ClockProbe.summary, this rank;
+    None without ``clock``)."""
     def loader():
         while True:
             yield from host_batches
@@ -351,18 +365,19 @@ def timed_steps(tr, host_batches, warmup, steps, world):
     if timer is not None:
         timer.clear()  # only the timed steps' launches count
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
-    probe = ClockProbe()
+    probe = ClockProbe() if clock else None
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    ck0 = probe.stamp()  # shader clock over the K steps: a stamp on each side, outside the step events
+    # shader clock over the K steps: a stamp on each side, outside the step events
+    ck0 = probe.stamp() if probe else None
     evs[0].record()
     last = None
     for i in range(steps):
         last = tr.step_async(next(it))
         evs[i + 1].record()
-    ck1 = probe.stamp()
+    ck1 = probe.stamp() if probe else None
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -372,7 +387,30 @@ def timed_steps(tr, host_batches, warmup, steps, world):
     if world > 1:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     tt = tt.cpu().tolist()
-    return tt[:-1], tt[-1], last, ClockProbe.summary(ClockProbe.mhz(ck0, ck1))
+    return tt[:-1], tt[-1], last, ClockProbe.summary(ClockProbe.mhz(ck0, ck1)) if probe else None
+
+
+DUMP_MAX_ELEMS = 4 << 20   # per array: 16 MB as float32, four arrays stay well under 64 MB
+
+
+def dump_outputs(dirname, tr, loss):
+    """What the last timed step computed, as ``dirname/<name>.npy`` (float32): the loss
+    Trainer.step_async returned and the state it left behind -- the flat parameters after
+    Adam, the flat gradient of that step and the BatchNorm running buffers.  An array above
+    DUMP_MAX_ELEMS is sampled at indices drawn once from a generator seeded by its length,
+    so two builds run with the same arguments write the same elements."""
+    import numpy as np
+    eng = tr.model.engine()
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = (("loss", loss.reshape(1)), ("params", eng.flat_p), ("grads", eng.flat_g),
+              ("bn_buffers", eng.flat_bn))
+    for name, t in arrays:
+        t = t.detach().reshape(-1).float().cpu()
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(t.numel())
+            t = t[torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values]
+        np.save(os.path.join(dirname, name + ".npy"), t.numpy())
 
 
 def main():
@@ -402,13 +440,16 @@ def main():
            "loss": "bce_dice", "precision": a.precision, "checkpoint_decoder": a.ckpt_decoder}
     tr = Trainer(cfg)
     host = _pinned_batches(a.batch, spatial, rank, 2, a.zero_fill)
-    tr.model.engine().kernel_timer = {}
+    if a.full:
+        tr.model.engine().kernel_timer = {}
     dp_info = None
     if world > 1:
         sync = tr._grad_sync()[1]
         sync.exposed_events = []
-    ts, wall, last, clock = timed_steps(tr, host, a.warmup, a.steps, world)
-    timer = tr.model.engine().kernel_timer
+    ts, wall, last, clock = timed_steps(tr, host, a.warmup, a.steps, world, clock=a.full)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, tr, last)
+    timer = tr.model.engine().kernel_timer or {}
     tr.model.engine().kernel_timer = None
     if world > 1:
         # the all-reduce time the backward did not hide: HIP events on the compute stream
@@ -436,12 +477,12 @@ def main():
     vols_step = world * a.batch
     value = vols_step / med
     roof = stem_roofline(tr, a.batch, spatial, a.kernel_reps, in_step if len(in_step) == 2 else None) \
-        if rank == 0 else None
+        if a.full and rank == 0 else None
     if roof is not None and rank == 0:
         roof["clock_standalone"] = stem_clock(tr, a.batch, spatial)
     # the fp32 parity build (the one that meets the 1e-3 logit bar) on the same batches
     fp32 = None
-    if a.fp32_steps > 0 and a.precision != "fp32":
+    if a.full and a.fp32_steps > 0 and a.precision != "fp32":
         del tr
         torch.cuda.empty_cache()
         torch.manual_seed(0)
@@ -450,7 +491,7 @@ def main():
         fp32 = round(vols_step / statistics.median(ts32), 3)
         del tr32
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(a.batch, spatial)
     if rank == 0:
         vox = spatial[0] * spatial[1] * spatial[2]
