@@ -179,3 +179,17 @@ def call(name: str, *args):
 def query(name: str, *args) -> int:
     """Host-only helpers (no stream): sizes / counts."""
     return getattr(load(), name)(*args)
+
+
+# the process-global ``int f(int)`` switches that change a workspace size, a row count or a route
+SWITCHES = ("pcms_conv3_big_min_boxes", "pcms_conv3_big_max_wgs", "pcms_conv3_fwd_box_vol",
+            "pcms_conv3_small_box_mtw2", "pcms_conv3_wgrad_tg_maxbox", "pcms_conv3_wgrad_k16",
+            "pcms_conv3_wgrad_x6_dma", "pcms_conv3_wgrad_reduce_fused", "pcms_conv3_b16_nt8",
+            "pcms_stem_wgrad_dense", "pcms_convt_fwd_stream", "pcms_convt_wgrad_taps", "pcms_convt_reduce_fused",
+            "pcms_bn_bwd_rows_cap")
+
+
+def switches() -> tuple:
+    """Their current values (-1 only queries every one of them; 0 sets some), in SWITCHES order:
+    part of the engine's allocation key."""
+    return tuple(query(name, -1) for name in SWITCHES)

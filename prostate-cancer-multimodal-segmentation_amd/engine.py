@@ -20,7 +20,7 @@ from __future__ import annotations
 import contextlib
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -34,12 +34,49 @@ BN_MOMENTUM = 0.1
 _DT = {"bf16": (torch.bfloat16, BF16), "fp32": (torch.float32, F32)}
 
 
+class Route(NamedTuple):
+    """How one 3x3x3 conv launch (a forward, or a dgrad = the forward of the mirrored weights)
+    runs at the laid-out shape; decided once by UNetEngine._route."""
+    kind: str     # "stem" | "b16" (16x16x32 kernel) | "b16_split" | "gen" (general kernel) | "gen_split"
+    splits: int   # split-K request of UNetEngine._splits (the general kernel's argument)
+    slabs: int    # slabs the general kernel resolves it to (pcms_conv3_splits; 1: unsplit)
+    slabs16: int  # slabs of the 16x16x32 split form (pcms_conv3_fwd16_split_ok; 0: it does not run)
+    rows: int     # BatchNorm partial rows the launch writes
+    pack16: bool  # a 16x16x32 form runs the layer: its pack16 weights are kept ("b16*" read them,
+    #               "gen*" the general kernel's pack)
+
+
+class Layout(NamedTuple):
+    """Everything that shapes one training step, fixed when UNetEngine._alloc lays out the
+    buffers for a forward: the backward, the checkpointed recompute and every launch read it,
+    never the engine's live attributes (a setting changed after a forward takes effect at the
+    next one).  The fields up to ``switches`` are the allocation key (UNetEngine.buf_key)."""
+    N: int
+    D: int
+    H: int
+    W: int
+    act_ckpt: bool
+    side_min_level: int
+    convt_wgrad_side: bool
+    pool_bn_apply_fused: bool
+    wgrad_target: int
+    split_target: int
+    fuse_bnin: bool
+    use_b16: bool
+    switches: Tuple[int, ...]           # _lib.switches(): the library's size / route switches
+    fwd: Tuple[Route, ...] = ()         # per conv (self.convs order = UNetEngine._sites order)
+    dgrad: Tuple[Optional[Route], ...] = ()  # None: the stem (its input needs no gradient)
+    bnin: Tuple[bool, ...] = ()         # per block (enc + dec): BN0 + ReLU fused into the second conv
+    pool_rows: Tuple[int, ...] = ()     # per level 0-3: partial rows of pcms_maxpool_bwd_bn
+
+
 class ConvSpec:
     __slots__ = ("mod", "cin", "cout", "cin_store", "fwd", "dgrad", "code", "fwd16", "dgrad16", "old_stale",
-                 "old_used")
+                 "old_used", "i")
 
     def __init__(self, mod, cin, cout, cin_store):
         self.mod, self.cin, self.cout, self.cin_store = mod, cin, cout, cin_store
+        self.i = None  # index in UNetEngine.convs (and in Layout.fwd / .dgrad)
         self.fwd = None
         self.dgrad = None
         # pcms_conv3_pack16 forms for the 16x16x32 big-box kernel (pcms_conv3_fwd16), set by
@@ -111,8 +148,8 @@ class UNetEngine:
         for b in self.enc + self.dec:
             self.convs += [b.c0, b.c1]
             self.bns += [b.b0, b.b1]
-        for cs in self.convs:
-            cs.code = self.code
+        for i, cs in enumerate(self.convs):
+            cs.code, cs.i = self.code, i
         self.convt_packs: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
         # bf16 build: the stem runs on dedicated tap-packed kernels (HBM-bound)
         self.stem_fast = self.code == BF16 and self.cp == 8
@@ -125,15 +162,11 @@ class UNetEngine:
         # pass, on the layers both kernels run (levels 0-1, bf16); bit-identical to the unfused
         # pair (same arithmetic and rounding).  False: the a1 pass (A/B)
         self.fuse_bnin = True
-        self._bnin_cache = {}
         # the level-0/1 convs (forward and dgrad) on the 16x16x32 big-box kernel
         # (pcms_conv3_fwd16, pack16 weights rebuilt with the other packs); PCMS_B16=0 keeps the
         # 32x32x16 big-box kernel (A/B)
         self.use_b16 = os.environ.get("PCMS_B16", "1") != "0"
         self._p16 = None  # pcms_conv3_pack16 table for the allocated shape
-        # the blocks whose training forward ran fused (id(BlockSpec)): the backward and the
-        # checkpointed recompute follow the forward's decision, not the current settings
-        self._fwd_bnin = set()
         self.stem_pack = None
         self._flat_ptrs = None
         self._packed_version = -1
@@ -141,8 +174,12 @@ class UNetEngine:
         self._packs_fresh = False  # the fused Adam wrote every conv / ConvT pack (not the stem's)
         self._stem_conv_stale = False  # the stem's general-kernel pack skipped by the fast path
         self._adam_plan = None
+        # the settings below (with fuse_bnin / use_b16 above) are read once per forward, into the
+        # allocation key (forward()); everything after follows self.layout, the plan _alloc made
+        # from them, so a change takes effect at the next forward
         self.bufs = None
         self.buf_key = None
+        self.layout: Optional[Layout] = None
         self.epoch = 0
         self.saved_epoch = -1
         # decoder activation checkpointing: the decoder blocks'
@@ -157,10 +194,10 @@ class UNetEngine:
         self.wgrad_target = 256  # conv weight-gradient workgroups: one round of 1 WG per CU (fewer partial rows to reduce than 512)
         self.grad_ready = None   # callable(lo, hi) per finished module gradient (dp.GradSync.ready)
         self.kernel_timer = None  # dict name -> [(start, end) events] (bench.py roofline timing)
-        self.wgrad_side_stream = False  # ablation: weight gradients on a side stream (measured 119.9 vs 121.6 vol/s: off)
         # levels >= this run their conv weight gradients on the side stream (the deep levels'
         # small latency-bound launches beside the dgrad chain; the big levels' persistent grids
-        # straggle when they share the chip).  99: never
+        # straggle when they share the chip).  99: never; 0: all of them (measured 119.9 vs
+        # 121.6 vol/s: off)
         self.wgrad_side_min_level = 99
         # the ConvTranspose weight + bias gradient (HBM-bound: it streams the up-path gradient,
         # 268 MB at level 0) on the side stream beside the same layer's ConvT dgrad (also
@@ -174,10 +211,6 @@ class UNetEngine:
         # where the per-voxel apply it replaces runs at ~6.2; profiles/r6_pool_bn_apply_fused_ab.txt):
         # off, i.e. pcms_maxpool_bwd_bn + pcms_bn_relu_bwd_finish
         self.pool_bn_apply_fused = False
-        # ablation only (tests/tools/step_ab.py nopack): skip the input pack, so the stem reads
-        # the previous step's packed input -- bounds what folding pack_input into the stem
-        # kernels could save; never set in the product (the forward is wrong with it)
-        self.ablate_skip_pack_input = False
         self._side_stream = None
         self._side_used = False
         # eval mode: every BatchNorm folded into the conv before it (pcms_bn_fold) and the ReLU
@@ -299,11 +332,8 @@ class UNetEngine:
     # weight gradients run on a side stream beside the data-gradient chain (dgrad -> BN ->
     # dgrad ...): they only read activations and the dY buffer of their layer, which the main
     # stream does not overwrite before the next _join_side()
-    def _side_at(self, lvl: int) -> bool:
-        return self.wgrad_side_stream or lvl >= self.wgrad_side_min_level
-
     def _side(self, lvl: int, on: Optional[bool] = None):
-        if not (self._side_at(lvl) if on is None else on):
+        if not (lvl >= self.layout.side_min_level if on is None else on):
             return contextlib.nullcontext()
         if self._side_stream is None:
             self._side_stream = torch.cuda.Stream(device=self.device)
@@ -589,18 +619,18 @@ class UNetEngine:
         cs = self.convs[i]
         pack, bias = self._eval[i]
         RELU = 2  # PCMS_CONV_RELU
-        splits = self._splits(N, S, c0 + c1, cs.cout, cs.code)
-        if i == 0 and self.stem_sup & 1:
-            call("pcms_stem_fwd", x0, self._eval["stem"], bias, a, None, N, S[0], S[1], S[2], RELU | self.stem_dense)
-        elif splits == 1:
+        r = self.layout.fwd[i]  # the stem kernel or the general one, whatever the training route
+        if r.kind == "stem":
+            call("pcms_stem_fwd", x0, self._eval["stem"], bias, a, None, N, *S, RELU | self.stem_dense)
+        elif r.splits == 1:
             call("pcms_conv3_fwd", cs.code, x0, c0, x1, c1, pack, bias, a, None, cs.cout, None, None, RELU,
-                 N, S[0], S[1], S[2], cs.cout, 1)
+                 N, *S, cs.cout, 1)
         else:
             acc = self.bufs["yacc"]
             call("pcms_conv3_fwd", cs.code, x0, c0, x1, c1, pack, bias, a, None, cs.cout, acc, None, 0,
-                 N, S[0], S[1], S[2], cs.cout, splits)
-            call("pcms_split_epilogue", self.code, acc, query("pcms_conv3_splits", cs.code, c0 + c1, splits),
-                 bias, a, None, cs.cout, None, cs.cout, N * S[0] * S[1] * S[2], RELU)
+                 N, *S, cs.cout, r.splits)
+            call("pcms_split_epilogue", self.code, acc, r.slabs, bias, a, None, cs.cout, None, cs.cout,
+                 N * S[0] * S[1] * S[2], RELU)
 
     # ------------------------------------------------------------------ buffers
     def _levels(self, D, H, W):
@@ -610,14 +640,54 @@ class UNetEngine:
             s.append((d // 2, h // 2, w // 2))
         return s
 
-    def _alloc(self, N, D, H, W):
-        # the workspaces below are sized for the current split / weight-gradient workgroup
-        # targets: a changed target re-lays them out (a larger one would otherwise overrun them)
-        key = (N, D, H, W, self.act_ckpt, self.wgrad_side_stream, self.wgrad_side_min_level, self.wgrad_target,
-               self.split_target, self.convt_wgrad_side)
-        if self.buf_key == key:
-            return
-        self.bufs = None
+    def _sites(self):
+        """The 18 conv call sites in self.convs order: (ConvSpec, level, c0, c1), c0 / c1 the
+        channels of the two sources as the block feeds them (the decoder's first conv reads
+        the skip and the upsampled halves)."""
+        for blk, l in [(bk, i) for i, bk in enumerate(self.enc)] + [(bk, 3 - i) for i, bk in enumerate(self.dec)]:
+            c1 = 64 << l if blk in self.dec else 0
+            yield blk.c0, l, blk.c0.cin_store - c1, c1
+            yield blk.c1, l, blk.c1.cin_store, 0
+
+    def _route(self, N, S, c0, c1, cout, code, b16: bool, dgrad: bool = False, stem: bool = False,
+               bnin: bool = False) -> Route:
+        """The kernel that runs conv(c0 + c1 -> cout) at N x S, its slab and row counts.  ``b16``:
+        the 16x16x32 forms may run it.  ``dgrad``: the dgrad's order of preference (it tries the
+        unsplit general kernel before the 16x16x32 split form; the forward after).  ``stem``:
+        the dedicated stem forward runs it.  ``bnin``: BN0 + ReLU in the staging (self._bnin):
+        the unsplit 16x16x32 kernel where the layer has a pack16 form, else the general one."""
+        splits = self._splits(N, S, c0 + c1, cout, code)
+        slabs = query("pcms_conv3_splits", code, c0 + c1, splits) if splits > 1 else 1
+        ok16 = b16 and bool(query("pcms_conv3_big16_ok", N, *S, c0, c1, cout))
+        sp16 = query("pcms_conv3_fwd16_split_ok", N, *S, c0, c1, cout) if b16 else 0
+        pack16 = ok16 or sp16 > 0
+        if stem:
+            kind = "stem"
+        elif bnin:
+            kind = "b16" if pack16 else "gen"
+        else:
+            ladder = [("b16", splits == 1 and ok16), ("b16_split", sp16 > 0), ("gen", splits == 1), ("gen_split", True)]
+            if dgrad:
+                ladder[1], ladder[2] = ladder[2], ladder[1]
+            kind = next(k for k, ok in ladder if ok)
+        if kind == "stem":
+            rows = query("pcms_stem_fwd_rows", N, *S)
+        elif kind == "b16":
+            rows = query("pcms_conv3_fwd16_rows", N, *S, c0, c1, cout)
+        elif kind == "gen":
+            rows = query("pcms_conv3_fwd_rows", code, N, *S, c0, c1, cout)
+        else:  # the split forms: the epilogue that sums the slabs writes them
+            rows = query("pcms_split_epilogue_rows", N * S[0] * S[1] * S[2])
+        return Route(kind, splits, slabs, sp16, rows, pack16)
+
+    def _alloc(self, key):
+        """Lay out the buffers and the step (self.layout) for ``key``, the Layout fields up to
+        ``switches``.  The workspaces are sized for the key's split / weight-gradient workgroup
+        targets and library switches: a changed one re-lays them out (a larger one would
+        otherwise overrun them)."""
+        L = Layout(*key)
+        N, D, H, W = key[:4]
+        self.bufs = self.layout = self.buf_key = None
         S = self._levels(D, H, W)
         if min(S[4]) < 1:
             raise ValueError(f"spatial size {(D, H, W)} is too small for 4 poolings")
@@ -637,11 +707,11 @@ class UNetEngine:
             for k in ("y1", "a1", "y2", "x"):
                 b[f"e{l}_{k}"] = act(l, C[l])
         for l in range(4):
-            for k in (("u", "a2") if self.act_ckpt else ("u", "y1", "a1", "y2", "a2")):
+            for k in (("u", "a2") if L.act_ckpt else ("u", "y1", "a1", "y2", "a2")):
                 # the last decoder block's ReLU output is never stored: the head applies that
                 # BatchNorm + ReLU itself (pcms_head_bn_fwd / _bwd)
                 b[f"d{l}_{k}"] = act(l, C[l]) if (l, k) != (0, "a2") else None
-        if self.act_ckpt:  # shared decoder set (level 0 is the largest: bytes per level ~ 4^-l)
+        if L.act_ckpt:  # shared decoder set (level 0 is the largest: bytes per level ~ 4^-l)
             for k in ("y1", "a1", "y2"):
                 b[f"ck_{k}"] = act(0, C[0])
         # gradient buffers
@@ -650,45 +720,50 @@ class UNetEngine:
             b[f"gA{l}"] = act(l, C[l])      # grad of a1 / block outputs (scratch)
             b[f"gY{l}"] = act(l, C[l])      # grad of pre-BN conv outputs (scratch)
             # second one while the side stream may still read gY; else an alias
-            b[f"gZ{l}"] = act(l, C[l]) if self._side_at(l) else b[f"gY{l}"]
+            b[f"gZ{l}"] = act(l, C[l]) if l >= L.side_min_level else b[f"gY{l}"]
             b[f"gU{l}"] = act(l, C[l])      # grad of up output / pooled input (scratch)
-        # workspaces
+        # dedicated stem kernels where they support the shape (else the general conv kernels)
+        self.stem_sup = query("pcms_stem_supported", N, D, H, W) if self.stem_fast else 0
+        # the conv call sites: routes, and what each needs of the shared workspaces
+        b16 = L.use_b16 and self.code == BF16
+        bnin = tuple(self._bnin(blk, N, S[l]) for blk, l in zip(self.enc + self.dec, (0, 1, 2, 3, 4, 3, 2, 1, 0)))
         rows_f = max(max(query("pcms_conv3_mblocks", N, *S[l]) for l in range(5)),
                      query("pcms_stem_fwd_rows", N, *S[0]))
-        for blk, l in [(bk, i) for i, bk in enumerate(self.enc)] + [(bk, 3 - i) for i, bk in enumerate(self.dec)]:
-            for cs, c1 in ((blk.c0, C[l] if blk in self.dec else 0), (blk.c1, 0)):
-                rows_f = max(rows_f, query("pcms_conv3_fwd16_rows", N, *S[l], cs.cin_store - c1, c1, cs.cout))
+        # weight-gradient workspace: per-split partial rows of the largest conv (and the stem)
+        ws = [query("pcms_stem_wgrad_ws_floats", N, *S[0], self.nmod)] if self.stem_fast else [1]
+        yacc = 1  # split-K slabs [slabs][nvox][Cout] of every conv (fwd and dgrad) that splits
+        fwd, dgrad = [], []
+        for cs, l, c0, c1 in self._sites():
+            stem = cs.i == 0  # it runs on its own kernels or the general one, and has no dgrad
+            rows_f = max(rows_f, query("pcms_conv3_fwd16_rows", N, *S[l], c0, c1, cs.cout))
+            ws.append(query("pcms_conv3_wgrad_ws_floats", cs.code, N, *S[l], c0, c1, cs.cout, L.wgrad_target))
+            fwd.append(self._route(N, S[l], c0, c1, cs.cout, cs.code, b16 and not stem,
+                                   stem=stem and bool(self.stem_sup & 1), bnin=cs.i % 2 == 1 and bnin[cs.i // 2]))
+            dgrad.append(None if stem else self._route(N, S[l], cs.cout, 0, cs.cin, cs.code, b16, dgrad=True))
+            # the 16x16x32 kernel's weight forms, where it can run the layer
+            cs.fwd16 = cs.dgrad16 = None
+            if fwd[-1].pack16:
+                cs.fwd16 = torch.empty(query("pcms_conv3_pack16_elems", cs.cout, cs.cin), dtype=T, device=dev)
+            if dgrad[-1] is not None and dgrad[-1].pack16:
+                cs.dgrad16 = torch.empty(query("pcms_conv3_pack16_elems", cs.cin, cs.cout), dtype=T, device=dev)
+            # both split forms of either direction, whichever the route takes (_conv_eval always
+            # takes the general one)
+            for r, cout in ((fwd[-1], cs.cout), (dgrad[-1], cs.cin)):
+                if r is not None:
+                    yacc = max(yacc, (r.slabs if r.splits > 1 else 0) * nv[l] * cout, r.slabs16 * nv[l] * cout)
+            cs.old_used = False
         rows_s = max(query("pcms_split_epilogue_rows", nv[l]) for l in range(5))
         rows_b = max(query("pcms_bn_bwd_rows", self.code, C[l], nv[l]) for l in range(5))
         # BN partials [rows][C][2] + [rows] voxel counts
         # (also the fused head's BatchNorm partial rows [rows_h][64][2])
         rows_h = query("pcms_head_bn_bwd_rows", D * H * W, N)
-        rows_b = max([rows_b] + [query("pcms_maxpool_bwd_bn_rows", self.code, N, *S[l], C[l]) for l in range(4)])
+        pool_rows = tuple(query("pcms_maxpool_bwd_bn_rows", self.code, N, *S[l], C[l]) for l in range(4))
+        rows_b = max(rows_b, *pool_rows)
         b["stats"] = torch.empty(max(max(rows_f, rows_s, rows_b) * (1024 * 2 + 1), rows_h * 64 * 2),
                                  dtype=torch.float32, device=dev)
         b["coef"] = torch.empty(3 * 1024, dtype=torch.float32, device=dev)
         b["bnws"] = torch.empty(query("pcms_bn_ws_doubles", 1024), dtype=torch.float64, device=dev)
-        # weight-gradient workspace: per-split partial rows of the largest conv (and the stem)
-        ws = [query("pcms_stem_wgrad_ws_floats", N, *S[0], self.nmod)] if self.stem_fast else [1]
-        for blk, l in [(bk, i) for i, bk in enumerate(self.enc)] + [(bk, 3 - i) for i, bk in enumerate(self.dec)]:
-            for cs, c1 in ((blk.c0, C[l] if blk in self.dec else 0), (blk.c1, 0)):
-                c0 = cs.cin_store - c1
-                ws.append(query("pcms_conv3_wgrad_ws_floats", cs.code, N, *S[l], c0, c1, cs.cout,
-                                self.wgrad_target))
         b["dwt"] = torch.empty(max(ws), dtype=torch.float32, device=dev)
-        # split-K slabs [splits][nvox][Cout] for every conv (fwd and dgrad) that splits
-        yacc = 1
-        for blk, l in [(bk, i) for i, bk in enumerate(self.enc)] + [(bk, 3 - i) for i, bk in enumerate(self.dec)]:
-            for cs, c1 in ((blk.c0, C[l] if blk in self.dec else 0), (blk.c1, 0)):
-                # forward (sources as the block feeds them: the decoder's first conv reads the
-                # skip and the upsampled halves), dgrad (the stem has none)
-                dirs = [(cs.cin_store - c1, c1, cs.cout)] + ([(cs.cout, 0, cs.cin)] if cs is not self.convs[0] else [])
-                for c0_, c1_, cout in dirs:
-                    sp = self._splits(N, S[l], c0_ + c1_, cout, cs.code)
-                    if sp > 1:
-                        yacc = max(yacc, query("pcms_conv3_splits", cs.code, c0_ + c1_, sp) * nv[l] * cout)
-                    if self.use_b16 and self.code == BF16:  # the level-3 16x16x32 split-K form
-                        yacc = max(yacc, query("pcms_conv3_fwd16_split_ok", N, *S[l], c0_, c1_, cout) * nv[l] * cout)
         b["yacc"] = torch.empty(yacc, dtype=torch.float32, device=dev)
         # partial rows of the head / ConvT-bias gradient reductions (summed in a fixed order)
         red = [query("pcms_head_bwd_ws_floats", D * H * W, N, self.ncls)]
@@ -697,11 +772,9 @@ class UNetEngine:
             red.append(query("pcms_convt_wgrad_bias_ws_floats", self.code, N, *S[l + 1], up.in_channels,
                              up.out_channels, 512))
         b["redws"] = torch.empty(max(red), dtype=torch.float32, device=dev)
-        # dedicated stem kernels where they support the shape (else the general conv kernels)
-        self.stem_sup = query("pcms_stem_supported", N, D, H, W) if self.stem_fast else 0
         ctws = [query("pcms_convt_wgrad_ws_floats", N, *S[4 - i], up.in_channels, up.out_channels, 512)
                 for i, up in enumerate(self.ups)]
-        if self.convt_wgrad_side:  # the weight gradient's rows apart: the dgrad runs beside it
+        if L.convt_wgrad_side:  # the weight gradient's rows apart: the dgrad runs beside it
             b["ctws_w"] = torch.empty(max(ctws), dtype=torch.float32, device=dev)
             ctws = []
         # the ConvT dgrad's K slabs share it (the weight gradient has reduced it by then)
@@ -711,31 +784,18 @@ class UNetEngine:
         ctws += [query("pcms_convt_fwd_ws_floats", N, *S[4 - i], up.in_channels, up.out_channels)
                  for i, up in enumerate(self.ups)]
         b["ctws"] = torch.empty(max(ctws), dtype=torch.float32, device=dev)
-        # the 16x16x32 big-box kernel: forward (sources as the block feeds them) and dgrad
-        for cs in self.convs:
-            cs.fwd16 = cs.dgrad16 = None
-        if self.use_b16 and self.code == BF16:
-            for blk, l in [(bk, i) for i, bk in enumerate(self.enc)] + [(bk, 3 - i) for i, bk in enumerate(self.dec)]:
-                for cs, c1 in ((blk.c0, C[l] if blk in self.dec else 0), (blk.c1, 0)):
-                    if cs is self.convs[0]:
-                        continue  # the stem runs on its own kernels
-                    c0 = cs.cin_store - c1
-                    if query("pcms_conv3_big16_ok", N, *S[l], c0, c1, cs.cout) or \
-                            query("pcms_conv3_fwd16_split_ok", N, *S[l], c0, c1, cs.cout):
-                        cs.fwd16 = torch.empty(query("pcms_conv3_pack16_elems", cs.cout, cs.cin), dtype=T, device=dev)
-                    if query("pcms_conv3_big16_ok", N, *S[l], cs.cout, 0, cs.cin) or \
-                            query("pcms_conv3_fwd16_split_ok", N, *S[l], cs.cout, 0, cs.cin):
-                        cs.dgrad16 = torch.empty(query("pcms_conv3_pack16_elems", cs.cin, cs.cout), dtype=T, device=dev)
-        for cs in self.convs:
-            cs.old_used = False
         self._p16 = None
         self._dirty = True  # build the new pack16 forms before the next conv
         self._packs_fresh = False  # (those of the last fused Adam went to the old buffers)
         self._adam_plan = None
         self.bufs = b
         self.buf_key = key
+        self.layout = L._replace(fwd=tuple(fwd), dgrad=tuple(dgrad), bnin=bnin, pool_rows=pool_rows)
 
     # ------------------------------------------------------------------ primitives
+    # _splits and _bnin follow the live split_target / wgrad_target / fuse_bnin: the engine
+    # calls them only from _alloc (through _route), within the forward that read those into the
+    # key, so Layout's routes are their answers; after that they serve as host-side queries
     def _splits(self, N, S, cin, cout, code):
         mb = query("pcms_conv3_mblocks", N, *S)
         wgs = mb * (cout // 64)
@@ -748,14 +808,41 @@ class UNetEngine:
         """The block's first BN + ReLU fused into its second conv (forward and weight gradient)?"""
         if not self.fuse_bnin or self.code != BF16:
             return False
-        key = (id(blk), N, tuple(S), self.wgrad_target, self.split_target)
-        if key not in self._bnin_cache:
-            # only where the unfused conv runs unsplit (the same big-box kernel, so the fused
-            # step stays bit-identical to the unfused one)
-            self._bnin_cache[key] = bool(query("pcms_conv3_bnin_ok", N, *S, blk.c1.cin, blk.c1.cout,
-                                               self.wgrad_target)) and \
-                self._splits(N, S, blk.c1.cin, blk.c1.cout, self.code) == 1
-        return self._bnin_cache[key]
+        # only where the unfused conv runs unsplit (the same big-box kernel, so the fused step
+        # stays bit-identical to the unfused one)
+        return bool(query("pcms_conv3_bnin_ok", N, *S, blk.c1.cin, blk.c1.cout, self.wgrad_target)) and \
+            self._splits(N, S, blk.c1.cin, blk.c1.cout, self.code) == 1
+
+    def _launch(self, r: Route, cs: ConvSpec, pack16, pack, x0, c0, x1, c1, bias, y0, y1, cy0, cout, st, N, S,
+                bnin: Optional[BNSpec] = None):
+        """One conv on route ``r``: (y0 | y1, split at channel cy0) = conv(x0 | x1) + bias with
+        ``cout`` output channels and BatchNorm partial rows into ``st`` -- a forward (``pack16``
+        / ``pack`` = cs.fwd16 / cs.fwd) or a dgrad (cs.dgrad16 / cs.dgrad).  ``bnin``: the input
+        is the pre-BN y1 of that BatchNorm; conv(relu(bn(x)))."""
+        nvox = N * S[0] * S[1] * S[2]
+        isc, ish = (bnin.scale, bnin.shift) if bnin is not None else (None, None)
+        if r.kind == "stem":
+            with self._timed("stem_fwd"):
+                call("pcms_stem_fwd", x0, self.stem_pack, bias, y0, st, N, *S, self.stem_dense)
+        elif r.kind == "b16":
+            call("pcms_conv3_fwd16", x0, c0, x1, c1, isc, ish, pack16, bias, y0, y1, cy0, st, 0, N, *S, cout)
+        elif r.kind == "b16_split":
+            acc = self.bufs["yacc"]
+            call("pcms_conv3_fwd16_split", x0, c0, x1, c1, pack16, acc, N, *S, cout, r.slabs16)
+            call("pcms_split_epilogue", self.code, acc, r.slabs16, bias, y0, y1, cy0, st, cout, nvox, 0)
+        else:  # the general kernel and its packs (rebuilt here when the fused Adam skipped them)
+            if cs.i == 0:
+                self._stem_conv_pack()
+            self._old_packs(cs)
+            if bnin is not None:
+                call("pcms_conv3_fwd_bnin", cs.code, x0, c0, isc, ish, pack, bias, y0, st, N, *S, cout)
+            elif r.kind == "gen":
+                call("pcms_conv3_fwd", cs.code, x0, c0, x1, c1, pack, bias, y0, y1, cy0, None, st, 0, N, *S, cout, 1)
+            else:
+                acc = self.bufs["yacc"]
+                call("pcms_conv3_fwd", cs.code, x0, c0, x1, c1, pack, bias, y0, y1, cy0, acc, None, 0, N, *S, cout,
+                     r.splits)
+                call("pcms_split_epilogue", self.code, acc, r.slabs, bias, y0, y1, cy0, st, cout, nvox, 0)
 
     def _conv(self, cs: ConvSpec, x0, c0, x1, c1, y, N, S, stats: bool, training: bool, bn: BNSpec,
               recompute: bool = False, bnin: Optional[BNSpec] = None):
@@ -764,47 +851,9 @@ class UNetEngine:
         ``bnin``: the input is the pre-BN y1 of that BatchNorm; conv(relu(bn(x)))."""
         b = self.bufs
         nvox = N * S[0] * S[1] * S[2]
-        splits = self._splits(N, S, c0 + c1, cs.cout, cs.code)
+        r = self.layout.fwd[cs.i]
         st = b["stats"] if training and not recompute else None
-        if cs is self.convs[0] and not self.stem_sup & 1:
-            self._stem_conv_pack()
-        if bnin is not None and cs.fwd16 is not None:
-            call("pcms_conv3_fwd16", x0, c0, None, 0, bnin.scale, bnin.shift, cs.fwd16, cs.mod.bias, y, None, cs.cout,
-                 st, 0, N, *S, cs.cout)
-            rows = query("pcms_conv3_fwd16_rows", N, *S, c0, 0, cs.cout)
-        elif bnin is not None:
-            self._old_packs(cs)
-            call("pcms_conv3_fwd_bnin", cs.code, x0, c0, bnin.scale, bnin.shift, cs.fwd, cs.mod.bias, y, st, N,
-                 *S, cs.cout)
-            rows = query("pcms_conv3_fwd_rows", cs.code, N, *S, c0, 0, cs.cout)
-        elif cs is self.convs[0] and self.stem_sup & 1:
-            with self._timed("stem_fwd"):
-                call("pcms_stem_fwd", x0, self.stem_pack, cs.mod.bias, y, st, N, S[0], S[1], S[2], self.stem_dense)
-            rows = query("pcms_stem_fwd_rows", N, *S)
-        elif splits == 1 and cs.fwd16 is not None and query("pcms_conv3_big16_ok", N, *S, c0, c1, cs.cout):
-            call("pcms_conv3_fwd16", x0, c0, x1, c1, None, None, cs.fwd16, cs.mod.bias, y, None, cs.cout, st, 0,
-                 N, S[0], S[1], S[2], cs.cout)
-            rows = query("pcms_conv3_fwd16_rows", N, *S, c0, c1, cs.cout)
-        elif cs.fwd16 is not None and (sp16 := query("pcms_conv3_fwd16_split_ok", N, *S, c0, c1, cs.cout)):
-            acc = b["yacc"]
-            if sp16 * nvox * cs.cout > acc.numel():
-                raise RuntimeError("split-K workspace smaller than the 16x16x32 split form needs")
-            call("pcms_conv3_fwd16_split", x0, c0, x1, c1, cs.fwd16, acc, N, *S, cs.cout, sp16)
-            call("pcms_split_epilogue", self.code, acc, sp16, cs.mod.bias, y, None, cs.cout, st, cs.cout, nvox, 0)
-            rows = query("pcms_split_epilogue_rows", nvox)
-        elif splits == 1:
-            self._old_packs(cs)
-            call("pcms_conv3_fwd", cs.code, x0, c0, x1, c1, cs.fwd, cs.mod.bias, y, None, cs.cout,
-                 None, st, 0, N, S[0], S[1], S[2], cs.cout, 1)
-            rows = query("pcms_conv3_fwd_rows", cs.code, N, *S, c0, c1, cs.cout)
-        else:
-            acc = b["yacc"]
-            self._old_packs(cs)
-            call("pcms_conv3_fwd", cs.code, x0, c0, x1, c1, cs.fwd, cs.mod.bias, y, None, cs.cout,
-                 acc, None, 0, N, S[0], S[1], S[2], cs.cout, splits)
-            call("pcms_split_epilogue", self.code, acc, query("pcms_conv3_splits", cs.code, c0 + c1, splits),
-                 cs.mod.bias, y, None, cs.cout, st, cs.cout, nvox, 0)
-            rows = query("pcms_split_epilogue_rows", nvox)
+        self._launch(r, cs, cs.fwd16, cs.fwd, x0, c0, x1, c1, cs.mod.bias, y, None, cs.cout, cs.cout, st, N, S, bnin)
         if recompute:
             return
         m = bn.mod
@@ -812,7 +861,7 @@ class UNetEngine:
             if nvox <= 1:
                 raise ValueError(f"Expected more than 1 value per channel when training, got input size "
                                  f"torch.Size([{N}, {bn.c}, {S[0]}, {S[1]}, {S[2]}])")
-            call("pcms_bn_finalize", st, rows, bn.c, float(nvox), m.weight, m.bias, m.running_mean,
+            call("pcms_bn_finalize", st, r.rows, bn.c, float(nvox), m.weight, m.bias, m.running_mean,
                  m.running_var, m.num_batches_tracked, BN_MOMENTUM, BN_EPS, bn.scale, bn.shift, bn.mean,
                  bn.invstd, b["bnws"])
         else:
@@ -831,7 +880,7 @@ class UNetEngine:
         if not training and self.fold_bn_eval:
             # eval: BN folded, ReLU in the epilogue; the last decoder block's output goes to its
             # y2 buffer, which the plain head then reads (forward(): self._eval_folded)
-            i0 = self.convs.index(blk.c0)
+            i0 = blk.c0.i
             a2 = out["a2"] if out["a2"] is not None else out["y2"]
             self._conv_eval(i0, x0, c0, x1, c1, out["a1"], N, S)
             self._conv_eval(i0 + 1, out["a1"], blk.c0.cout, None, 0, a2, N, S)
@@ -839,13 +888,7 @@ class UNetEngine:
                 call("pcms_maxpool_fwd", self.code, a2, pool_out, N, *S, blk.c1.cout)
             return
         self._conv(blk.c0, x0, c0, x1, c1, out["y1"], N, S, True, training, blk.b0, recompute)
-        if recompute:
-            bnin = id(blk) in self._fwd_bnin
-        else:
-            bnin = self._bnin(blk, N, S)
-            if training:
-                (self._fwd_bnin.add if bnin else self._fwd_bnin.discard)(id(blk))
-        if bnin:  # a1 is never stored: the second conv applies BN0 + ReLU itself
+        if self.layout.bnin[blk.c0.i // 2]:  # a1 is never stored: the second conv applies BN0 + ReLU itself
             self._conv(blk.c1, out["y1"], blk.c0.cout, None, 0, out["y2"], N, S, True, training, blk.b1, recompute,
                        bnin=blk.b0)
         else:
@@ -861,7 +904,7 @@ class UNetEngine:
 
     def _dec_acts(self, l: int) -> Dict[str, torch.Tensor]:
         b = self.bufs
-        if not self.buf_key[4]:  # the mode the buffers were laid out for
+        if not self.layout.act_ckpt:  # the mode the buffers were laid out for
             return {k: b[f"d{l}_{k}"] for k in ("y1", "a1", "y2", "a2")}
         n = b["nv"][l] * b["C"][l]
         return {"y1": b["ck_y1"][:n], "a1": b["ck_a1"][:n], "y2": b["ck_y2"][:n], "a2": b[f"d{l}_a2"]}
@@ -880,8 +923,12 @@ class UNetEngine:
             x = x.float()
         N, _, D, H, W = x.shape
         # buffers first: a (re)allocation decides which convs run on the 16x16x32 kernel and
-        # marks the packs dirty, so their pack16 forms are built by the _ensure_packs below
-        self._alloc(N, D, H, W)
+        # marks the packs dirty, so their pack16 forms are built by the _ensure_packs below.
+        # The one read of the step's settings and of the library's switches: the key
+        key = (N, D, H, W, self.act_ckpt, self.wgrad_side_min_level, self.convt_wgrad_side, self.pool_bn_apply_fused,
+               self.wgrad_target, self.split_target, self.fuse_bnin, self.use_b16, _lib.switches())
+        if key != self.buf_key:
+            self._alloc(key)
         self._ensure_packs()
         folded = not training and self.fold_bn_eval
         if folded:
@@ -890,8 +937,7 @@ class UNetEngine:
             self._bn_epoch += training
         b = self.bufs
         S, C = b["S"], b["C"]
-        if not self.ablate_skip_pack_input:
-            call("pcms_pack_input", self.code, x, b["xin"], N, self.nmod, D * H * W, self.cp)
+        call("pcms_pack_input", self.code, x, b["xin"], N, self.nmod, D * H * W, self.cp)
         # encoder
         inp, cin = b["xin"], self.cp
         for l in range(5):
@@ -937,6 +983,7 @@ class UNetEngine:
         they came from pcms_maxpool_bwd_bn_sums (ga2 holds the skip part only) and the apply
         adds the pooled gradient ``pool_dp`` itself (pcms_maxpool_bn_apply)."""
         b = self.bufs
+        wt = self.layout.wgrad_target
         nvox = N * S[0] * S[1] * S[2]
         # the previous block's weight gradients (side stream) read this level's buffers until
         # joined (a decoder and an encoder block share gY / gZ / gA at one level)
@@ -956,13 +1003,12 @@ class UNetEngine:
         if ga2 is not None:
             self._grads_done(blk.b1.mod.weight, blk.b1.mod.bias)
         with self._side(lvl):
-            if id(blk) in self._fwd_bnin:  # x = relu(bn0(y1)), applied in the kernel's staging (as the forward)
+            if self.layout.bnin[blk.c0.i // 2]:  # x = relu(bn0(y1)), applied in the kernel's staging (as the forward)
                 call("pcms_conv3_wgrad_bnin", blk.c1.code, acts["y1"], blk.c0.cout, blk.b0.scale, blk.b0.shift, gY,
-                     blk.c1.mod.weight.grad, b["dwt"], N, *S, blk.c1.cout, blk.c1.cin, self.wgrad_target,
-                     int(self._gstore))
+                     blk.c1.mod.weight.grad, b["dwt"], N, *S, blk.c1.cout, blk.c1.cin, wt, int(self._gstore))
             else:
                 call("pcms_conv3_wgrad", blk.c1.code, acts["a1"], blk.c0.cout, None, 0, gY, blk.c1.mod.weight.grad,
-                     b["dwt"], N, *S, blk.c1.cout, blk.c1.cin, self.wgrad_target, int(self._gstore))
+                     b["dwt"], N, *S, blk.c1.cout, blk.c1.cin, wt, int(self._gstore))
         self._grads_done(blk.c1.mod.weight, blk.c1.mod.bias)
         # dgrad conv1 -> grad of a1
         self._dgrad(blk.c1, gY, gA, None, blk.c1.cin, N, S)
@@ -982,12 +1028,8 @@ class UNetEngine:
         self._bn_bwd(blk.b0, gA, acts["y1"], gZ, nvox)
         self._grads_done(blk.b0.mod.weight, blk.b0.mod.bias)
         with self._side(lvl):
-            if blk is self.enc[0] and self.stem_sup & 2:
-                with self._timed("stem_wgrad"):
-                    call("pcms_stem_wgrad", x0, gZ, blk.c0.mod.weight.grad, b["dwt"], blk.c0.cin, N, *S)
-            else:
-                call("pcms_conv3_wgrad", blk.c0.code, x0, c0, x1, c1, gZ, blk.c0.mod.weight.grad, b["dwt"], N,
-                     *S, blk.c0.cout, blk.c0.cin, self.wgrad_target, int(self._gstore))
+            call("pcms_conv3_wgrad", blk.c0.code, x0, c0, x1, c1, gZ, blk.c0.mod.weight.grad, b["dwt"], N,
+                 *S, blk.c0.cout, blk.c0.cin, wt, int(self._gstore))
         self._grads_done(blk.c0.mod.weight, blk.c0.mod.bias)
         if gx_out0 is not None:
             self._dgrad(blk.c0, gZ, gx_out0, gx_out1, cy0, N, S)
@@ -999,37 +1041,15 @@ class UNetEngine:
              b["stats"], b["coef"], m.weight.grad, m.bias.grad, gy, bn.c, nvox, b["bnws"])
 
     def _dgrad(self, cs: ConvSpec, gy, out0, out1, cy0, N, S):
-        b = self.bufs
-        nvox = N * S[0] * S[1] * S[2]
-        splits = self._splits(N, S, cs.cout, cs.cin, cs.code)
-        if splits == 1 and cs.dgrad16 is not None and query("pcms_conv3_big16_ok", N, *S, cs.cout, 0, cs.cin):
-            call("pcms_conv3_fwd16", gy, cs.cout, None, 0, None, None, cs.dgrad16, None, out0, out1, cy0, None, 0,
-                 N, *S, cs.cin)
-        elif splits == 1:
-            self._old_packs(cs)
-            call("pcms_conv3_fwd", cs.code, gy, cs.cout, None, 0, cs.dgrad, None, out0, out1, cy0,
-                 None, None, 0, N, *S, cs.cin, 1)
-        elif cs.dgrad16 is not None and (sp16 := query("pcms_conv3_fwd16_split_ok", N, *S, cs.cout, 0, cs.cin)):
-            acc = b["yacc"]
-            if sp16 * nvox * cs.cin > acc.numel():
-                raise RuntimeError("split-K workspace smaller than the 16x16x32 split form needs")
-            call("pcms_conv3_fwd16_split", gy, cs.cout, None, 0, cs.dgrad16, acc, N, *S, cs.cin, sp16)
-            call("pcms_split_epilogue", self.code, acc, sp16, None, out0, out1, cy0, None, cs.cin, nvox, 0)
-        else:
-            acc = b["yacc"]
-            self._old_packs(cs)
-            call("pcms_conv3_fwd", cs.code, gy, cs.cout, None, 0, cs.dgrad, None, out0, out1, cy0,
-                 acc, None, 0, N, *S, cs.cin, splits)
-            call("pcms_split_epilogue", self.code, acc, query("pcms_conv3_splits", cs.code, cs.cout, splits),
-                 None, out0, out1, cy0, None, cs.cin, nvox, 0)
+        """(out0 | out1, split at channel cy0) = the gradient of the input of conv ``cs``."""
+        self._launch(self.layout.dgrad[cs.i], cs, cs.dgrad16, cs.dgrad, gy, cs.cout, None, 0, None, out0, out1, cy0,
+                     cs.cin, None, N, S)
 
     def backward(self, dlogits: torch.Tensor):
         if self.saved_epoch != self.epoch:
             raise RuntimeError("UNet3D backward must follow its own training forward (the engine keeps "
                                "only the activations of the latest forward)")
-        if self.buf_key[7:9] != (self.wgrad_target, self.split_target):
-            raise RuntimeError("wgrad_target / split_target changed between the forward and its backward (the "
-                               "workspaces were sized for the forward's values)")
+        L = self.layout  # the forward's: the buffers were laid out for it, whatever the settings are now
         fresh = self.sync_params(full=False, fresh_ok=True)
         self._gstore = fresh
         if fresh:
@@ -1037,7 +1057,7 @@ class UNetEngine:
             call("pcms_fill_ranges", self.flat_g, ranges, nr, mx, 0.0)
         b = self.bufs
         S, C = b["S"], b["C"]
-        N = self.buf_key[0]
+        N = L.N
         dlogits = dlogits.contiguous().float()
         oc = self.model.outc
         D, H, W = S[0]
@@ -1058,7 +1078,7 @@ class UNetEngine:
             blk = self.dec[i]
             acts = self._dec_acts(l)
             self._join_side()  # the recompute rewrites the shared set the side stream may still read
-            if self.buf_key[4]:
+            if L.act_ckpt:
                 self._block_fwd(blk, b[f"e{l}_x"], C[l], b[f"d{l}_u"], C[l], acts, N, S[l], True, recompute=True)
             gu = b[f"gU{l}"]
             self._block_bwd(blk, g, acts, b[f"e{l}_x"], C[l], b[f"d{l}_u"], C[l], b[f"gx{l}"], gu, C[l], N,
@@ -1068,9 +1088,9 @@ class UNetEngine:
             hin = b["e4_x"] if i == 0 else b[f"d{l + 1}_a2"]
             # weight and bias gradients in one pass over gu (the bias sum over the ConvT output
             # box, F.pad's front offsets floor((S[l] - 2 S[l + 1]) / 2))
-            with self._side(l, self.convt_wgrad_side):
+            with self._side(l, L.convt_wgrad_side):
                 call("pcms_convt_wgrad_bias", self.code, hin, gu, up.weight.grad, up.bias.grad,
-                     b["ctws_w"] if self.convt_wgrad_side else b["ctws"], b["redws"], N, *S[l + 1], up.in_channels,
+                     b["ctws_w"] if L.convt_wgrad_side else b["ctws"], b["redws"], N, *S[l + 1], up.in_channels,
                      up.out_channels, *S[l], 512)
             self._grads_done(up.weight, up.bias)
             gnext = b["gx4"] if i == 0 else b[f"gA{l + 1}"]
@@ -1093,10 +1113,10 @@ class UNetEngine:
                 # (fused form: the pooled gradient is added again by that block's BN apply, so
                 # the block output's gradient gx{l-1} is not rewritten)
                 bn = self.enc[l - 1].b1
-                call("pcms_maxpool_bwd_bn_sums" if self.pool_bn_apply_fused else "pcms_maxpool_bwd_bn", self.code,
+                call("pcms_maxpool_bwd_bn_sums" if L.pool_bn_apply_fused else "pcms_maxpool_bwd_bn", self.code,
                      b[f"e{l - 1}_y2"], bn.scale, bn.shift, bn.mean, bn.invstd, gp, b[f"gx{l - 1}"], b["stats"], N,
                      *S[l - 1], C[l - 1])
-                pool_dp = gp if self.pool_bn_apply_fused else None
-                rows = query("pcms_maxpool_bwd_bn_rows", self.code, N, *S[l - 1], C[l - 1])
+                pool_dp = gp if L.pool_bn_apply_fused else None
+                rows = L.pool_rows[l - 1]
         self._join_side()  # every weight gradient before the optimizer / all-reduce wait
         self.saved_epoch = -1

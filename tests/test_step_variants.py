@@ -482,3 +482,144 @@ def test_pool_bn_apply_fused_step_bit_identical(precision, S):
         runs.append(out + [eng.flat_p.clone(), eng.flat_bn.clone()])
     for a, b in zip(*runs):
         assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("setting", ["wgrad_target", "split_target", "convt_wgrad_side", "checkpoint_decoder"])
+def test_backward_runs_from_its_forwards_layout(setting):
+    """A setting changed between a training forward and its backward takes effect at the next
+    forward: the backward runs from the layout its forward made (engine.layout), so its gradients
+    equal, bit for bit, those of a run that had not changed the setting yet, and after the
+    optimizer step a second full step equals that of the run that changed the setting after its
+    first backward (2 x 5x32x32x32 bf16: levels 0-4 all run split-K there).  Only the directions
+    whose wrong reading could not write past a buffer: wgrad_target 256 -> 128, split_target
+    512 -> 256, convt_wgrad_side off -> on, checkpoint_decoder off -> on.  The two target cases
+    are not vacuous at this shape: the split counts and the weight-gradient workspace sizes of
+    the conv call sites differ between the two values (asserted on the host)."""
+    from pcms_amd import _lib as L
+    from pcms_amd.models.unet3d import UNet3D
+    from pcms_amd.optim import FlatAdam
+    from pcms_amd.utils.losses import BCEDiceLoss
+    N, S0 = 2, (32, 32, 32)
+    gen = torch.Generator().manual_seed(11)
+    x = torch.rand(N, 5, *S0, generator=gen).cuda()
+    y = (torch.rand(N, 1, *S0, generator=gen) < 0.4).float().cuda()
+    new = {"wgrad_target": 128, "split_target": 256, "convt_wgrad_side": True, "checkpoint_decoder": True}[setting]
+    field = "act_ckpt" if setting == "checkpoint_decoder" else setting
+    crit = BCEDiceLoss()
+    runs = []
+    for before_backward in (True, False):
+        torch.manual_seed(0)
+        m = UNet3D(n_modalities=5, n_classes=1).cuda()
+        eng = m.engine()
+        opt = FlatAdam(m, lr=1e-3, weight_decay=1e-5)
+        opt.zero_grad()
+        loss = crit(m(x), y)
+        lay = eng.layout
+        assert getattr(lay, field) != new
+        if before_backward:
+            setattr(m if setting == "checkpoint_decoder" else eng, setting, new)
+        loss.backward()
+        assert eng.layout is lay
+        g1 = eng.flat_g.clone()
+        if not before_backward:
+            setattr(m if setting == "checkpoint_decoder" else eng, setting, new)
+        opt.step()
+        opt.zero_grad()
+        lg = m(x)
+        assert getattr(eng.layout, field) == new  # the next forward re-laid out
+        loss = crit(lg, y)
+        loss.backward()
+        out = [g1, lg.detach().clone(), loss.detach().clone(), eng.flat_g.clone()]
+        opt.step()
+        torch.cuda.synchronize()
+        runs.append(out + [eng.flat_p.clone(), eng.flat_bn.clone()])
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
+    S = eng.bufs["S"]
+    if setting == "split_target":
+        def splits(target):
+            eng.split_target = target
+            return [eng._splits(N, S[l], c0 + c1, cs.cout, cs.code) for cs, l, c0, c1 in eng._sites()]
+        assert splits(512) != splits(256)
+    if setting == "wgrad_target":
+        ws = [[L.query("pcms_conv3_wgrad_ws_floats", cs.code, N, *S[l], c0, c1, cs.cout, t)
+               for cs, l, c0, c1 in eng._sites()] for t in (256, 128)]
+        assert ws[0] != ws[1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ckpt", [False, True])
+def test_wgrad_side_levels_step_bit_identical(ckpt):
+    """The conv weight gradients of levels >= 0 and >= 3 on the side stream
+    (engine.wgrad_side_min_level; those levels then get a gZ buffer of their own, the others
+    keep gZ aliased to gY: both from the layout) give the same two bf16 training steps bit for
+    bit as the serial order: logits, losses, every gradient, the Adam updates and the BatchNorm
+    buffers (2 x 64x64x32; with and without decoder checkpointing)."""
+    from pcms_amd.models.unet3d import UNet3D
+    from pcms_amd.optim import FlatAdam
+    from pcms_amd.utils.losses import BCEDiceLoss
+    gen = torch.Generator().manual_seed(9)
+    x = torch.rand(2, 5, 64, 64, 32, generator=gen).cuda()
+    y = (torch.rand(2, 1, 64, 64, 32, generator=gen) < 0.4).float().cuda()
+    runs = []
+    for level in (99, 0, 3):
+        torch.manual_seed(0)
+        m = UNet3D(n_modalities=5, n_classes=1, checkpoint_decoder=ckpt).cuda()
+        eng = m.engine()
+        eng.wgrad_side_min_level = level
+        opt = FlatAdam(m, lr=1e-3, weight_decay=1e-5)
+        out = []
+        for _ in range(2):
+            opt.zero_grad()
+            lg = m(x)
+            loss = BCEDiceLoss()(lg, y)
+            loss.backward()
+            g = eng.flat_g.clone()
+            opt.step()
+            out += [lg.detach().clone(), loss.detach().clone(), g]
+        torch.cuda.synchronize()
+        assert [eng.bufs[f"gZ{l}"] is eng.bufs[f"gY{l}"] for l in range(5)] == [l < level for l in range(5)]
+        runs.append(out + [eng.flat_p.clone(), eng.flat_bn.clone()])
+    for other in runs[1:]:
+        for a, b in zip(runs[0], other):
+            assert torch.equal(a, b)
+
+
+@pytest.mark.gpu
+def test_library_switch_relays_out():
+    """The library's size / route switches are part of the allocation key: after one training
+    step (2 x 5x32x32x32 bf16) pcms_bn_bwd_rows_cap is doubled, and the next forward lays the
+    buffers out again (a new ``bufs``) and the step's loss and gradients are finite.  (At this
+    size the row counts stay under either cap.)"""
+    from pcms_amd import _lib as L
+    from pcms_amd.models.unet3d import UNet3D
+    from pcms_amd.optim import FlatAdam
+    from pcms_amd.utils.losses import BCEDiceLoss
+    gen = torch.Generator().manual_seed(12)
+    x = torch.rand(2, 5, 32, 32, 32, generator=gen).cuda()
+    y = (torch.rand(2, 1, 32, 32, 32, generator=gen) < 0.4).float().cuda()
+    torch.manual_seed(0)
+    m = UNet3D(n_modalities=5, n_classes=1).cuda()
+    eng = m.engine()
+    opt = FlatAdam(m, lr=1e-3, weight_decay=1e-5)
+
+    def step():
+        opt.zero_grad()
+        loss = BCEDiceLoss()(m(x), y)
+        loss.backward()
+        opt.step()
+        return loss.detach()
+
+    step()
+    bufs = eng.bufs
+    cap = L.query("pcms_bn_bwd_rows_cap", -1)
+    try:
+        L.query("pcms_bn_bwd_rows_cap", 2 * cap)
+        loss = step()
+        torch.cuda.synchronize()
+        assert eng.bufs is not bufs
+        assert eng.layout.switches == L.switches() and 2 * cap in eng.layout.switches
+        assert math.isfinite(float(loss)) and torch.isfinite(eng.flat_g).all()
+    finally:
+        L.query("pcms_bn_bwd_rows_cap", cap)
