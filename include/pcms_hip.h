@@ -175,6 +175,20 @@ int pcms_stem_wgrad(const void* x, const void* dy, float* dw, float* ws, int cin
 int pcms_stem_wgrad_bn(const void* x, const void* da, const void* y, const float* scale, const float* shift,
                        const float* mean, const float* invstd, const float* coef, float* dw, float* ws, int cin_w,
                        int N, int D, int H, int W, hipStream_t s);
+/* The stem conv's input gradient (models/unet3d.py:29 inc.conv.0 under autograd: aten
+ * convolution_backward's grad_input, which the reference forms whenever the model input
+ * requires grad -- saliency, adversarial inputs, a differentiable pre-processing in front):
+ *   dx[n][ci][d][h][w] = sum_{co, kd, kh, kw} dy[n][d+1-kd][h+1-kh][w+1-kw][co] W[co][ci][kd][kh][kw]
+ * dy: NDHWC, 64 channels, storage type; dx: fp32 NCDHW [N][cin_w][D][H][W], every element
+ * written exactly once with plain stores (no zero fill, no atomics, fp32 accumulation: two runs
+ * are bit-identical).  wpack: pcms_stem_dgrad_pack of the fp32 master weight [64][cin_w][27]
+ * (pcms_stem_dgrad_pack_elems(dtype) elements of the storage type).  Any N, D, H, W >= 1 with
+ * dy below 2 GiB (-7 otherwise); cin_w <= 8.  bf16: v_mfma_f32_16x16x32_bf16, weights as the
+ * A operand; fp32: plain fmaf.                                                            */
+int pcms_stem_dgrad_pack_elems(int dtype);
+int pcms_stem_dgrad_pack(int dtype, const float* w, void* out, int cin_w, hipStream_t s);
+int pcms_stem_dgrad(int dtype, const void* dy, const void* wpack, float* dx, int N, int D, int H, int W, int cin_w,
+                    hipStream_t s);
 /* y = sum of the `splits` slabs of acc (in split order) + bias -> storage type; stats
  * layout as pcms_conv3_fwd with rows = pcms_split_epilogue_rows(nvox)                    */
 int pcms_split_epilogue_rows(long nvox);
@@ -200,6 +214,14 @@ int pcms_bn_eval_coeffs(const float* gamma, const float* beta, const float* rmea
                         float eps, int C, float* scale, float* shift, hipStream_t s);
 int pcms_bn_relu(int dtype, const void* y, void* a, const float* scale, const float* shift, int C,
                  long nvox, hipStream_t s);
+/* Eval-mode BatchNorm3d + ReLU backward (models/unet3d.py:31-39 with the module in eval():
+ * aten native_batch_norm_backward(train=False) + threshold_backward, as autograd runs them
+ * for an input gradient): dy = da * scale[c] where y * scale[c] + shift[c] > 0 (the forward's
+ * own fp32 expression, pcms_bn_relu), else 0; scale / shift from pcms_bn_eval_coeffs.  A pure
+ * apply: running statistics are constants, so there is no reduction and no parameter
+ * gradient.                                                                                */
+int pcms_bn_relu_bwd_eval(int dtype, const void* da, const void* y, const float* scale, const float* shift,
+                          void* dy, int C, long nvox, hipStream_t s);
 /* A/B switch: block cap of the BN-backward reduce passes (their partial rows): 512 (default,
  * the one-launch finalize) or more (2048: the two-stage finalize); v <= 0 queries; returns the
  * previous value; set before the workspace queries */
@@ -325,6 +347,12 @@ int pcms_head_bn_bwd(int dtype, const void* y, const float* scale, const float* 
                      const float* invstd, const float* gamma, const float* dlogits, const float* w, float* dw,
                      float* db, float* ws, float* bnpart, float* coef, float* dgamma, float* dbeta, void* dy,
                      long nvox_per_n, int N, int ncls, double* bnws, hipStream_t s);
+/* Eval-mode input-gradient backward of pcms_head_bn_fwd (models/unet3d.py:222, :295 outc and
+ * :37-39 up4's last BatchNorm3d + ReLU in eval(), under autograd): dy[v][c] = (sum_k
+ * dlogits[k][v] w[k][c]) * scale[c] where y * scale[c] + shift[c] > 0, else 0 -- the gradient of
+ * the block's pre-BN conv output y in one pass; no parameter gradient is written.           */
+int pcms_head_bn_bwd_eval(int dtype, const void* y, const float* scale, const float* shift, const float* dlogits,
+                          const float* w, void* dy, long nvox_per_n, int N, int ncls, hipStream_t s);
 
 /* ---- DiceLoss / BCEDiceLoss: utils/losses.py:44-92, 124-152 ------------------------ */
 int pcms_loss_rows(long M);

@@ -55,6 +55,11 @@ SIGNATURES = {
     "pcms_stem_wgrad_ws_floats": "iiiii",
     "pcms_stem_wgrad": "ppppiiiiis",
     "pcms_stem_wgrad_bn": "ppppppppppiiiiis",
+    "pcms_stem_dgrad_pack_elems": "i",
+    "pcms_stem_dgrad_pack": "ippis",
+    "pcms_stem_dgrad": "ipppiiiiis",
+    "pcms_bn_relu_bwd_eval": "ipppppils",
+    "pcms_head_bn_bwd_eval": "ippppppliis",
     "pcms_split_epilogue_rows": "l",
     "pcms_split_epilogue": "ipipppipilis",
     "pcms_bn_ws_doubles": "i",

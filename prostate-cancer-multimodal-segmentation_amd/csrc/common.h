@@ -138,7 +138,13 @@ template <bool NT, typename T> __device__ __forceinline__ void st16(T* p, const 
 // BatchNorm (train or eval coefficients) + ReLU of one element: the one expression every
 // kernel that applies it uses (bn_relu pass and the fused consumers), so a recomputed
 // activation equals the stored one bit for bit
-__device__ __forceinline__ float bn_relu1(float y, float sc, float sh) { return fmaxf(__builtin_fmaf(y, sc, sh), 0.f); }
+__device__ __forceinline__ float bn_pre(float y, float sc, float sh) { return __builtin_fmaf(y, sc, sh); }
+__device__ __forceinline__ float bn_relu1(float y, float sc, float sh) { return fmaxf(bn_pre(y, sc, sh), 0.f); }
+// eval-mode BatchNorm + ReLU backward of one element (running statistics: no reduction):
+// dy = da * sc where the forward's own expression bn_pre(y, sc, sh) is positive, else 0
+__device__ __forceinline__ float bn_bwd_eval_dy(float da, float y, float sc, float sh) {
+  return bn_pre(y, sc, sh) > 0.f ? da * sc : 0.f;
+}
 // ReLU of 8 packed bf16 values: negative ones (sign bit set) -> +0
 __device__ __forceinline__ u32x4_t relu_bf16x8(u32x4_t v) {
 #pragma unroll

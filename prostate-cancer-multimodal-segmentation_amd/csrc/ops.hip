@@ -388,6 +388,30 @@ __global__ void __launch_bounds__(TPB) bn_relu_bwd_apply_kernel(
 }
 
 // ---------------- MaxPool3d(2), floor mode; first max wins (PyTorch scan order) -------
+// Eval-mode BatchNorm + ReLU backward (running statistics, so the coefficients are constants:
+// a pure apply, no reduction): dy = da * scale where relu(y scale + shift) passed, else 0 -- the
+// mask from the forward's own expression (bn_bwd_eval_dy).  The input-gradient backward of an
+// eval forward (saliency): no parameter gradient is formed.
+template <typename T, bool NT>
+__global__ void __launch_bounds__(TPB) bn_relu_bwd_eval_kernel(const T* da, const T* y, const float* scale,
+                                                               const float* shift, T* dy, int C, long nvox) {
+  constexpr int VEC = Elem<T>::kVec;
+  const int CG = C / VEC;
+  const int cg = threadIdx.x % CG, vl = threadIdx.x / CG, VL = TPB / CG;
+  const int c0 = cg * VEC;
+  float sc[VEC], sh[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) { sc[j] = scale[c0 + j]; sh[j] = shift[c0 + j]; }
+  for (long v = (long)blockIdx.x * VL + vl; v < nvox; v += (long)gridDim.x * VL) {
+    float dv[VEC], yv[VEC], o[VEC];
+    ld16<NT>(da + v * C + c0, dv);
+    ld16<NT>(y + v * C + c0, yv);
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) o[j] = bn_bwd_eval_dy(dv[j], yv[j], sc[j], sh[j]);
+    st16<NT>(dy + v * C + c0, o);
+  }
+}
+
 template <typename T>
 __global__ void maxpool_fwd_kernel(const T* a, T* p, int N, int D, int H, int W, int C) {
   constexpr int VEC = Elem<T>::kVec;
@@ -1148,6 +1172,45 @@ __global__ void __launch_bounds__(TPB, 2) head_bn_apply_kernel(const T* y, const
   }
 }
 
+// Eval-mode backward of the fused head (head_fwd_kernel<BN>) down to the last decoder block's
+// pre-BN conv output y: dy[v, c] = (sum_k dl[k, v] w[k, c]) * scale[c] where relu(y scale +
+// shift) passed, else 0 (bn_bwd_eval_dy).  One pass over y and dlogits; the block's ReLU output
+// was never stored and no parameter gradient is written.
+template <typename T, bool NT, int NC>
+__global__ void __launch_bounds__(TPB, 2) head_bn_bwd_eval_kernel(const T* y, const float* dlogits, const float* w,
+                                                               const float* scale, const float* shift, T* dy,
+                                                               long nvox_per_n, int N) {
+  const long total = (long)N * nvox_per_n;
+  const int sub = threadIdx.x & 7;
+  float sc[8], sh[8], wk[NC][8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int c = sub * 8 + j;
+    sc[j] = scale[c]; sh[j] = shift[c];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) wk[k][j] = w[k * 64 + c];
+  }
+  const long stride = ((long)gridDim.x * blockDim.x) >> 3;
+  long v = (blockIdx.x * (long)blockDim.x + threadIdx.x) >> 3;
+  VoxQR pv(v, nvox_per_n);
+  for (; v < total; v += stride) {
+    float x[8], dl[NC], o[8];
+    head_ld<T, NT>(y + v * 64 + sub * 8, x);
+#pragma unroll
+    for (int k = 0; k < NC; ++k) dl[k] = dlogits[((long)pv.q * NC + k) * nvox_per_n + pv.r];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < NC; ++k)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] += dl[k] * wk[k][j];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = bn_bwd_eval_dy(o[j], x[j], sc[j], sh[j]);
+    head_st<T, NT>(dy + v * 64 + sub * 8, o);
+    pv.advance((uint32_t)stride);
+  }
+}
+
 // dw[k][c] += col (k, c), db[k] += col (k, 64) of the summed head partial rows
 __global__ void head_bwd_finish_kernel(const float* sums, int ncls, float* dw, float* db) {
   const int idx = threadIdx.x;
@@ -1481,6 +1544,16 @@ int launch_head_apply(bool nt, int grid, hipStream_t s, const void* y, const flo
   });
 }
 
+template <typename T>
+int launch_head_eval(bool nt, int grid, hipStream_t s, const void* y, const float* dl, const float* w, const float* sc,
+                     const float* sh, void* dy, long nvox_per_n, int N, int ncls) {
+  return with_ncls<1>(ncls, [&](auto nc) {
+    constexpr int NC = decltype(nc)::value;
+    hipLaunchKernelGGL((nt ? head_bn_bwd_eval_kernel<T, true, NC> : head_bn_bwd_eval_kernel<T, false, NC>), dim3(grid),
+                       dim3(TPB), 0, s, (const T*)y, dl, w, sc, sh, (T*)dy, nvox_per_n, N);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -1550,6 +1623,22 @@ int pcms_bn_relu(int dtype, const void* y, void* a, const float* scale, const fl
   else
     hipLaunchKernelGGL((nt ? bn_relu_kernel<float, true> : bn_relu_kernel<float, false>), dim3(grid), dim3(TPB), 0, s,
                        (const float*)y, (float*)a, scale, shift, C, nvox);
+  PCMS_CHECK_LAUNCH();
+}
+
+int pcms_bn_relu_bwd_eval(int dtype, const void* da, const void* y, const float* scale, const float* shift, void* dy,
+                          int C, long nvox, hipStream_t s) {
+  const int VEC = dtype == PCMS_BF16 ? 8 : 4;
+  if ((dtype != PCMS_BF16 && dtype != PCMS_F32) || C <= 0 || C % VEC || TPB % (C / VEC) || nvox < 1) return -1;
+  if (!da || !y || !scale || !shift || !dy) return -2;
+  const int grid = ew_grid(dtype, C, nvox);
+  const bool nt = nvox * C * (dtype == PCMS_BF16 ? 2 : 4) >= kNtBytesBn;
+  if (dtype == PCMS_BF16)
+    hipLaunchKernelGGL((nt ? bn_relu_bwd_eval_kernel<bf16_t, true> : bn_relu_bwd_eval_kernel<bf16_t, false>), dim3(grid),
+                       dim3(TPB), 0, s, (const bf16_t*)da, (const bf16_t*)y, scale, shift, (bf16_t*)dy, C, nvox);
+  else
+    hipLaunchKernelGGL((nt ? bn_relu_bwd_eval_kernel<float, true> : bn_relu_bwd_eval_kernel<float, false>), dim3(grid),
+                       dim3(TPB), 0, s, (const float*)da, (const float*)y, scale, shift, (float*)dy, C, nvox);
   PCMS_CHECK_LAUNCH();
 }
 
@@ -1849,6 +1938,21 @@ int pcms_head_bn_bwd(int dtype, const void* y, const float* scale, const float* 
     launch_head_apply<bf16_t>(nt, agrid, s, y, dlogits, w, scale, shift, mean, invstd, coef, dy, nvox_per_n, N, ncls);
   else
     launch_head_apply<float>(nt, agrid, s, y, dlogits, w, scale, shift, mean, invstd, coef, dy, nvox_per_n, N, ncls);
+  PCMS_CHECK_LAUNCH();
+}
+
+int pcms_head_bn_bwd_eval(int dtype, const void* y, const float* scale, const float* shift, const float* dlogits,
+                          const float* w, void* dy, long nvox_per_n, int N, int ncls, hipStream_t s) {
+  if ((long)N * nvox_per_n >= (1L << 31)) return -7;  // 32-bit index math in the kernel
+  if (ncls > 4 || ncls < 1 || N < 1 || nvox_per_n < 1 || (dtype != PCMS_BF16 && dtype != PCMS_F32)) return -1;
+  if (!y || !scale || !shift || !dlogits || !w || !dy) return -2;
+  const long nvox = (long)N * nvox_per_n;
+  const bool nt = nvox * 64 * (dtype == PCMS_BF16 ? 2 : 4) >= kNtBytes;
+  const int grid = grid_for(nvox * 8, TPB);
+  int rc;
+  if (dtype == PCMS_BF16) rc = launch_head_eval<bf16_t>(nt, grid, s, y, dlogits, w, scale, shift, dy, nvox_per_n, N, ncls);
+  else rc = launch_head_eval<float>(nt, grid, s, y, dlogits, w, scale, shift, dy, nvox_per_n, N, ncls);
+  if (rc) return rc;
   PCMS_CHECK_LAUNCH();
 }
 

@@ -13,7 +13,10 @@ in ONE flat fp32 master buffer (the module's nn.Parameters are views into it, so
 packs (bf16 / fp32, MFMA-friendly order) are rebuilt from the master when it changes.
 
 The engine keeps the activations of the LAST training forward; ``backward`` must follow
-that forward (checked).  Only device code runs: there is no CPU path.
+that forward (checked).  ``backward(dlogits, want_dx=True)`` also returns the gradient of the
+network input (the stem's dgrad, pcms_stem_dgrad).  An eval forward with ``keep_input_grad``
+keeps what ``backward_input`` needs for that gradient alone (saliency: no parameter
+gradient).  Only device code runs: there is no CPU path.
 """
 from __future__ import annotations
 
@@ -168,6 +171,11 @@ class UNetEngine:
         self.use_b16 = os.environ.get("PCMS_B16", "1") != "0"
         self._p16 = None  # pcms_conv3_pack16 table for the allocated shape
         self.stem_pack = None
+        # pcms_stem_dgrad's weight pack (the input gradient): built from the master on first
+        # use and again when the weights moved on (_stem_dgrad), so a step that asks for no
+        # input gradient launches and allocates nothing for it
+        self.stem_dpack = None
+        self._stem_dpack_key = None
         self._flat_ptrs = None
         self._packed_version = -1
         self._dirty = True
@@ -182,6 +190,8 @@ class UNetEngine:
         self.layout: Optional[Layout] = None
         self.epoch = 0
         self.saved_epoch = -1
+        self.saved_eval_epoch = -1  # the eval forward backward_input may follow (keep_input_grad)
+        self._folded = False        # the forward in progress runs the folded eval route
         # decoder activation checkpointing: the decoder blocks'
         # pre-BN conv outputs and first ReLU output (y1, a1, y2) are not kept per level; the
         # forward writes them into one shared level-0-sized set and the backward recomputes
@@ -877,7 +887,7 @@ class UNetEngine:
         (encoder blocks 0-3): the output is max-pooled into it in the same pass (the next
         Down3D's MaxPool3d, pcms_bn_relu_pool)."""
         nvox = N * S[0] * S[1] * S[2]
-        if not training and self.fold_bn_eval:
+        if not training and self._folded:
             # eval: BN folded, ReLU in the epilogue; the last decoder block's output goes to its
             # y2 buffer, which the plain head then reads (forward(): self._eval_folded)
             i0 = blk.c0.i
@@ -910,10 +920,15 @@ class UNetEngine:
         return {"y1": b["ck_y1"][:n], "a1": b["ck_a1"][:n], "y2": b["ck_y2"][:n], "a2": b[f"d{l}_a2"]}
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x: torch.Tensor, training: bool, act: int = 0, threshold: float = 0.5) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, training: bool, act: int = 0, threshold: float = 0.5,
+                keep_input_grad: bool = False) -> torch.Tensor:
         """The network on ``x`` (N, n_modalities, D, H, W).  ``act``: 0 logits, 1 sigmoid
         probabilities (predict), 2 ``sigmoid > threshold`` masks (inference), all produced
-        by the head kernel."""
+        by the head kernel.  ``keep_input_grad`` (eval): the unfolded eval route whatever
+        ``fold_bn_eval`` says -- the pre-BN conv outputs are stored and every BatchNorm's
+        scale / shift come from pcms_bn_eval_coeffs -- so that ``backward_input`` can follow."""
+        if keep_input_grad and training:
+            raise ValueError("keep_input_grad is the eval route; a training forward keeps its activations anyway")
         if x.dim() != 5 or x.shape[1] != self.nmod:
             raise ValueError(f"expected input (N, {self.nmod}, D, H, W), got {tuple(x.shape)}")
         if x.device != self.device:
@@ -930,7 +945,7 @@ class UNetEngine:
         if key != self.buf_key:
             self._alloc(key)
         self._ensure_packs()
-        folded = not training and self.fold_bn_eval
+        folded = self._folded = not training and self.fold_bn_eval and not keep_input_grad
         if folded:
             self._ensure_eval_packs()
         else:
@@ -970,18 +985,36 @@ class UNetEngine:
         self.epoch += 1
         if training:
             self.saved_epoch = self.epoch
+        elif keep_input_grad:
+            self.saved_eval_epoch = self.epoch
         return logits
 
     # ------------------------------------------------------------------ backward
+    def _stem_dgrad(self, dy1, N, S) -> torch.Tensor:
+        """dx (N, n_modalities, D, H, W) fp32 = the stem conv's input gradient of ``dy1`` (the
+        gradient of its pre-BN output), on the current stream."""
+        key = (self._wgen, self.flat_p._version)
+        if self.stem_dpack is None:
+            self.stem_dpack = torch.empty(query("pcms_stem_dgrad_pack_elems", self.code), dtype=self.tdtype,
+                                          device=self.device)
+        if key != self._stem_dpack_key:
+            call("pcms_stem_dgrad_pack", self.code, self.convs[0].mod.weight, self.stem_dpack, self.nmod)
+            self._stem_dpack_key = key
+        dx = torch.empty((N, self.nmod, *S), dtype=torch.float32, device=self.device)
+        with self._timed("stem_dgrad"):
+            call("pcms_stem_dgrad", self.code, dy1, self.stem_dpack, dx, N, *S, self.nmod)
+        return dx
+
     def _block_bwd(self, blk: BlockSpec, ga2, acts, x0, c0, x1, c1, gx_out0, gx_out1, cy0, N, S, lvl,
-                   bn1_rows: int = 0, pool_dp=None):
+                   bn1_rows: int = 0, pool_dp=None, want_dx: bool = False):
         """Backward of one DoubleConv block. ga2: grad of block output (None: the second
         BN + ReLU backward was already done by its consumer, gY{lvl} holds dy2).  Writes the
         grad of the block input into gx_out0 (channels [0, cy0)) / gx_out1 (rest); None = skip.
         ``bn1_rows``: the second BatchNorm's backward partial rows are already in the stats
         buffer (written by pcms_maxpool_bwd_bn), only its finish + apply run here.  ``pool_dp``:
         they came from pcms_maxpool_bwd_bn_sums (ga2 holds the skip part only) and the apply
-        adds the pooled gradient ``pool_dp`` itself (pcms_maxpool_bn_apply)."""
+        adds the pooled gradient ``pool_dp`` itself (pcms_maxpool_bn_apply).  ``want_dx`` (the
+        stem block): the gradient of the network input is formed too and returned."""
         b = self.bufs
         wt = self.layout.wgrad_target
         nvox = N * S[0] * S[1] * S[2]
@@ -1014,17 +1047,22 @@ class UNetEngine:
         self._dgrad(blk.c1, gY, gA, None, blk.c1.cin, N, S)
         # BN0/ReLU backward -> dy1 (a second buffer: the side stream may still read gY)
         if blk is self.enc[0] and self.stem_sup & 2:
-            # the stem: its BN0 apply runs inside the weight-gradient kernel (dy never stored)
+            # the stem: its BN0 apply runs inside the weight-gradient kernel (dy never stored) --
+            # unless the input gradient is wanted: then the apply pass also writes dy1 into gZ.
+            # Where gZ is gY's alias this level's weight gradients ran on this stream, so
+            # nothing on the side stream reads it (joined all the same)
             bn = blk.b0
             m = bn.mod
+            if want_dx and gZ is gY:
+                self._join_side()
             call("pcms_bn_relu_bwd", self.code, gA, acts["y1"], bn.scale, bn.shift, bn.mean, bn.invstd, m.weight,
-                 b["stats"], b["coef"], m.weight.grad, m.bias.grad, None, bn.c, nvox, b["bnws"])
+                 b["stats"], b["coef"], m.weight.grad, m.bias.grad, gZ if want_dx else None, bn.c, nvox, b["bnws"])
             self._grads_done(m.weight, m.bias)
             with self._side(lvl), self._timed("stem_wgrad"):
                 call("pcms_stem_wgrad_bn", x0, gA, acts["y1"], bn.scale, bn.shift, bn.mean, bn.invstd, b["coef"],
                      blk.c0.mod.weight.grad, b["dwt"], blk.c0.cin, N, *S)
             self._grads_done(blk.c0.mod.weight, blk.c0.mod.bias)
-            return
+            return self._stem_dgrad(gZ, N, S) if want_dx else None
         self._bn_bwd(blk.b0, gA, acts["y1"], gZ, nvox)
         self._grads_done(blk.b0.mod.weight, blk.b0.mod.bias)
         with self._side(lvl):
@@ -1033,6 +1071,9 @@ class UNetEngine:
         self._grads_done(blk.c0.mod.weight, blk.c0.mod.bias)
         if gx_out0 is not None:
             self._dgrad(blk.c0, gZ, gx_out0, gx_out1, cy0, N, S)
+        if want_dx:  # the stem on the general route: gZ holds dy1
+            return self._stem_dgrad(gZ, N, S)
+        return None
 
     def _bn_bwd(self, bn: BNSpec, ga, y, gy, nvox):
         b = self.bufs
@@ -1045,7 +1086,10 @@ class UNetEngine:
         self._launch(self.layout.dgrad[cs.i], cs, cs.dgrad16, cs.dgrad, gy, cs.cout, None, 0, None, out0, out1, cy0,
                      cs.cin, None, N, S)
 
-    def backward(self, dlogits: torch.Tensor):
+    def backward(self, dlogits: torch.Tensor, want_dx: bool = False) -> Optional[torch.Tensor]:
+        """The training backward: every parameter gradient into the flat gradient buffer.
+        ``want_dx``: also the gradient of the network input, returned as a fresh fp32 tensor
+        (N, n_modalities, D, H, W); the parameter gradients are the same bits either way."""
         if self.saved_epoch != self.epoch:
             raise RuntimeError("UNet3D backward must follow its own training forward (the engine keeps "
                                "only the activations of the latest forward)")
@@ -1098,13 +1142,13 @@ class UNetEngine:
                  up.out_channels, *S[l])
             g = gnext
         # encoder, deepest first; gx{l} holds the skip gradient already (l < 4)
-        rows, pool_dp = 0, None
+        rows, pool_dp, dx = 0, None, None
         for l in reversed(range(5)):
             blk = self.enc[l]
             acts = {"y1": b[f"e{l}_y1"], "a1": b[f"e{l}_a1"], "y2": b[f"e{l}_y2"]}
             if l == 0:
-                self._block_bwd(blk, b["gx0"], acts, b["xin"], self.cp, None, 0, None, None, 0, N, S[0], 0,
-                                bn1_rows=rows, pool_dp=pool_dp)
+                dx = self._block_bwd(blk, b["gx0"], acts, b["xin"], self.cp, None, 0, None, None, 0, N, S[0], 0,
+                                     bn1_rows=rows, pool_dp=pool_dp, want_dx=want_dx)
             else:
                 gp = b[f"gU{l}"]
                 self._block_bwd(blk, b[f"gx{l}"], acts, b[f"pool{l}"], C[l - 1], None, 0, gp, None, C[l - 1], N,
@@ -1120,3 +1164,68 @@ class UNetEngine:
                 rows = L.pool_rows[l - 1]
         self._join_side()  # every weight gradient before the optimizer / all-reduce wait
         self.saved_epoch = -1
+        return dx
+
+    # ------------------------------------------------------------------ eval input gradient
+    def _block_bwd_input(self, blk: BlockSpec, ga2, acts, gx_out0, gx_out1, cy0, N, S, lvl, stem: bool = False):
+        """_block_bwd without the weight gradients and BatchNorm reductions (eval: running
+        statistics are constants): BN1 + ReLU backward (``ga2`` None: gY{lvl} holds dy2 already),
+        conv1 dgrad, BN0 + ReLU backward, conv0 dgrad -- or, ``stem``, pcms_stem_dgrad, whose
+        result is returned."""
+        b = self.bufs
+        nvox = N * S[0] * S[1] * S[2]
+        gY, gZ, gA = b[f"gY{lvl}"], b[f"gZ{lvl}"], b[f"gA{lvl}"]
+        if ga2 is not None:
+            call("pcms_bn_relu_bwd_eval", self.code, ga2, acts["y2"], blk.b1.scale, blk.b1.shift, gY, blk.b1.c, nvox)
+        self._dgrad(blk.c1, gY, gA, None, blk.c1.cin, N, S)
+        call("pcms_bn_relu_bwd_eval", self.code, gA, acts["y1"], blk.b0.scale, blk.b0.shift, gZ, blk.b0.c, nvox)
+        if stem:
+            return self._stem_dgrad(gZ, N, S)
+        self._dgrad(blk.c0, gZ, gx_out0, gx_out1, cy0, N, S)
+        return None
+
+    def backward_input(self, dlogits: torch.Tensor) -> torch.Tensor:
+        """The gradient of the network input after an eval forward with ``keep_input_grad``: the
+        training schedule minus every weight gradient and BatchNorm reduction.  No parameter
+        gradient is read or written."""
+        if self.saved_eval_epoch != self.epoch:
+            raise RuntimeError("UNet3D input-gradient backward must follow its own eval forward (the engine "
+                               "keeps only the activations of the latest forward)")
+        L = self.layout
+        b = self.bufs
+        S, C = b["S"], b["C"]
+        N = L.N
+        D, H, W = S[0]
+        dlogits = dlogits.contiguous().float()
+        self._join_side()
+        bn = self.dec[3].b1
+        call("pcms_head_bn_bwd_eval", self.code, self._dec_acts(0)["y2"], bn.scale, bn.shift, dlogits,
+             self.model.outc.weight, b["gY0"], D * H * W, N, self.ncls)
+        g = None
+        for i in reversed(range(4)):
+            l = 3 - i
+            blk = self.dec[i]
+            acts = self._dec_acts(l)
+            if L.act_ckpt:
+                self._block_fwd(blk, b[f"e{l}_x"], C[l], b[f"d{l}_u"], C[l], acts, N, S[l], True, recompute=True)
+            gu = b[f"gU{l}"]
+            self._block_bwd_input(blk, g, acts, b[f"gx{l}"], gu, C[l], N, S[l], l)
+            up = self.ups[i]
+            _, dpack = self.convt_packs[i]
+            gnext = b["gx4"] if i == 0 else b[f"gA{l + 1}"]
+            call("pcms_convt_dgrad_ws", self.code, gu, dpack, gnext, b["ctws"], N, *S[l + 1], up.in_channels,
+                 up.out_channels, *S[l])
+            g = gnext
+        dx = None
+        for l in reversed(range(5)):
+            acts = {"y1": b[f"e{l}_y1"], "a1": b[f"e{l}_a1"], "y2": b[f"e{l}_y2"]}
+            if l == 0:
+                dx = self._block_bwd_input(self.enc[0], b["gx0"], acts, None, None, 0, N, S[0], 0, stem=True)
+            else:
+                gp = b[f"gU{l}"]
+                self._block_bwd_input(self.enc[l], b[f"gx{l}"], acts, gp, None, C[l - 1], N, S[l], l)
+                # MaxPool3d backward into the skip gradient gx{l-1} (the stored block output
+                # e{l-1}_x gives the arg-max)
+                call("pcms_maxpool_bwd", self.code, b[f"e{l - 1}_x"], gp, b[f"gx{l - 1}"], N, *S[l - 1], C[l - 1])
+        self.saved_eval_epoch = -1
+        return dx

@@ -76,6 +76,7 @@ class _UNetFunction(torch.autograd.Function):
         ctx.engine = engine
         ctx.epoch = engine.epoch
         ctx.nparams = len(params)
+        ctx.x_dtype = x.dtype
         return logits
 
     @staticmethod
@@ -83,8 +84,34 @@ class _UNetFunction(torch.autograd.Function):
         if ctx.engine.epoch != ctx.epoch:
             raise RuntimeError("UNet3D: another forward ran before this graph's backward; "
                                "the engine keeps only the latest forward's activations")
-        ctx.engine.backward(dlogits)
-        return (None, None) + (None,) * ctx.nparams
+        dx = ctx.engine.backward(dlogits, want_dx=ctx.needs_input_grad[0])
+        if dx is not None and dx.dtype != ctx.x_dtype:
+            dx = dx.to(ctx.x_dtype)
+        return (dx, None) + (None,) * ctx.nparams
+
+
+class _UNetEvalFunction(torch.autograd.Function):
+    """Autograd node of one eval forward whose input requires grad (saliency / attribution,
+    adversarial inputs): backward yields the input gradient only -- BatchNorm runs on its
+    running statistics and no parameter gradient is produced."""
+
+    @staticmethod
+    def forward(ctx, x, engine):
+        logits = engine.forward(x, training=False, keep_input_grad=True)
+        ctx.engine = engine
+        ctx.epoch = engine.epoch
+        ctx.x_dtype = x.dtype
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        if ctx.engine.epoch != ctx.epoch:
+            raise RuntimeError("UNet3D: another forward ran before this graph's backward; "
+                               "the engine keeps only the latest forward's activations")
+        dx = ctx.engine.backward_input(dlogits)
+        if dx.dtype != ctx.x_dtype:
+            dx = dx.to(ctx.x_dtype)
+        return dx, None
 
 
 class UNet3D(nn.Module):
@@ -151,12 +178,16 @@ class UNet3D(nn.Module):
         return st
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """Training mode with grad enabled: one autograd node whose backward writes every
+        ``param.grad`` and, when ``x`` requires grad, returns ``x.grad`` too.  Eval mode with
+        grad enabled and ``x.requires_grad``: the logits hang on a node whose backward yields
+        ``x.grad`` only (fp32 values, in ``x``'s dtype) -- parameter gradients are NOT produced
+        in eval mode, ``param.grad`` is left as it is.  Otherwise the logits carry no graph."""
         eng = self.engine()
         if self.training and torch.is_grad_enabled():
             return _UNetFunction.apply(x, eng, *eng.params)
-        if not self.training and torch.is_grad_enabled() and any(p.requires_grad for p in eng.params) \
-                and x.requires_grad:
-            raise NotImplementedError("eval-mode backward is not supported by the HIP engine")
+        if not self.training and torch.is_grad_enabled() and x.requires_grad:
+            return _UNetEvalFunction.apply(x, eng)
         with torch.no_grad():
             return eng.forward(x, training=self.training)
 

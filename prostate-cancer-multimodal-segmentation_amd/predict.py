@@ -9,7 +9,9 @@
 * ``ModelPredictor(model_path, device)``: UNet3D(n_modalities=5, n_classes=1) with either
   checkpoint form (:121-145), ``predict`` -> (D, H, W) probabilities from ``UNet3D.predict``
   (sigmoid in the head kernel, :160-170), ``save_prediction`` -> uint8 ``> 0.5`` mask NIfTI
-  with the reference image's voxel spacing when one is given (:172-196).
+  with the reference image's voxel spacing when one is given (:172-196).  ``saliency`` ->
+  (5, D, H, W) input gradient of the summed probabilities (no reference equivalent in
+  predict.py; plain autograd through the reference model gives the same quantity).
 """
 from __future__ import annotations
 
@@ -66,6 +68,16 @@ class ModelPredictor:
         with torch.no_grad():
             out = self.model.predict(image_tensor.to(self.device))
         return out.squeeze(0).squeeze(0).cpu().numpy()
+
+    def saliency(self, image_tensor: torch.Tensor) -> np.ndarray:
+        """Input attribution of one case: d(sum of sigmoid(logits)) / d(input) as a (5, D, H, W)
+        float32 array -- which modality and which voxels drive the predicted lesion volume.
+        Eval mode (running BatchNorm statistics); no parameter gradient is touched."""
+        x = image_tensor.to(self.device).float().detach().requires_grad_(True)
+        self.model.eval()
+        with torch.enable_grad():
+            torch.sigmoid(self.model(x)).sum().backward()
+        return x.grad.squeeze(0).float().cpu().numpy()
 
     def save_prediction(self, prediction: np.ndarray, output_path: str,
                         reference_image_path: Optional[str] = None) -> None:
