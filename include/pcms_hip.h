@@ -412,6 +412,26 @@ int pcms_add(int dtype, void* dst, const void* src, long n, hipStream_t s);
  * (DoubleConv3D / Down3D / Up3D called on their own, models/unet3d.py:42-158)          */
 int pcms_unpack_output(int dtype, const void* in, float* out, int N, int C, int Cs, long V, hipStream_t s);
 
+/* ---- loader: data.resample on the device (script/data_loader.py:240-283, :379-409) --- */
+/* One source volume -> one D x H x W fp32 plane (a channel of an NCDHW tensor), equal to
+ * data.resample of the decoded volume bit for bit.  src: the file's voxels in their native
+ * type, little endian, (Di, Hi, Wi) with W fastest, aligned to the element size; datatype: the
+ * NIfTI-1 code (2 u8, 4 i16, 8 i32, 16 f32, 64 f64, 256 i8, 512 u16, 768 u32, 1024 i64, 1280
+ * u64).  A voxel's value is (float)((double)raw * slope + inter) when scl_slope is not 0 or 1
+ * or scl_inter is not 0 (slope 0 meaning 1), else (float)raw.  Output index i of an axis
+ * samples c = (double)i * ((double)n_in / n_out): neighbours floor(c), floor(c) + 1 clamped to
+ * the volume, fp64 lerps a (1 - w) + b w over D, then H, then W (no FMA contraction), one
+ * rounding to fp32; 0 where c >= n_in - 0.5 on any axis; an axis with n_in == n_out is copied.
+ * An unknown datatype, a dimension < 1, a NULL or misaligned pointer: negative, no launch.  */
+int pcms_resample_linear(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope, double scl_inter,
+                         float* out, int D, int H, int W, hipStream_t s);
+/* The label form: index k = floor((double)i * ratio + 0.5) per axis (identity when n_in ==
+ * n_out), out = 0 where k >= n_in, else (value > 0 ? 1 : 0) with the value scaled in fp64 as
+ * above and, as data.resample returns fp32, rounded to fp32 before the comparison unless the
+ * volume already has the target shape (ProstateDataset compares that one as read).        */
+int pcms_resample_label(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope, double scl_inter,
+                        float* out, int D, int H, int W, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

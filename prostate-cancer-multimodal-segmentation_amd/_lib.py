@@ -115,6 +115,8 @@ SIGNATURES = {
     "pcms_grad_clip": "plffippps",
     "pcms_add": "ippls",
     "pcms_unpack_output": "ippiiils",
+    "pcms_resample_linear": "piiiiddpiiis",
+    "pcms_resample_label": "piiiiddpiiis",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

@@ -259,3 +259,8 @@ __device__ __forceinline__ float sum_rows16(const float* src, long step, int n) 
 #define PCMS_CHECK_LAUNCH() return (int)hipGetLastError()
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+// blocks of a grid-stride launch: one per per_block units of work, between 1 and cap
+static inline int grid_for(long work, int per_block, int cap = 8192) {
+  const long g = (work + per_block - 1) / per_block;
+  return (int)(g < 1 ? 1 : g > cap ? cap : g);
+}

@@ -18,10 +18,6 @@ namespace {
 
 constexpr int TPB = 256;
 
-inline int grid_for(long work, int per_block, int cap = 8192) {
-  return (int)std::max<long>(1, std::min<long>(cap, (work + per_block - 1) / per_block));
-}
-
 // ---------------- input: NCDHW fp32 (N, Cin, V) -> NDHWC T (N, V, Cp) ----------------
 template <typename T>
 __global__ void pack_input_kernel(const float* in, T* out, int N, int Cin, long V, int Cp) {

@@ -1,0 +1,194 @@
+// Device-side resampling of one NIfTI volume to the training grid (gfx950): the loader's
+// data.resample (the reference's ResampleImageFilter geometry, script/data_loader.py:258-281
+// linear for images, :383-406 nearest for labels) evaluated per output voxel, bit for bit.
+//
+// The source is the file's voxel bytes in their native type (NIfTI datatype code, little
+// endian, (Di, Hi, Wi) with W fastest); the header's scl_slope / scl_inter are applied on the
+// fly by read_nifti's rule.  Output index i of an axis samples the continuous input index
+// c = (double)i * (n_in / n_out), the fp64 expression numpy forms (exact rational indices
+// disagree with it for many size pairs).  data.resample runs three separable fp64 passes
+// (D, then H, then W); an 8-corner gather lerped in that order gives every intermediate the
+// same two operands and so the same roundings.  Every product and sum below must round on its
+// own, as numpy's do: no contraction into FMAs anywhere in this file.
+#include "common.h"
+#include "pcms_hip.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int TPB = 256;
+
+// One axis of the output grid, formed on the host: ratio = (double)n_in / (double)n_out (numpy's
+// n_in / n_out), edge = n_in - 0.5 (zero from there on), ident: n_in == n_out (the pass is skipped)
+struct Axis {
+  double ratio, edge;
+  int n_in, n_out, ident;
+};
+struct Scale {
+  double slope, inter;
+  int on;  // read_nifti: slope not in (0, 1) or inter != 0, with slope 0 meaning 1
+};
+
+inline Axis make_axis(int n_in, int n_out) {
+  return Axis{(double)n_in / (double)n_out, (double)n_in - 0.5, n_in, n_out, n_in == n_out ? 1 : 0};
+}
+inline Scale make_scale(double slope, double inter) {
+  const int on = (!(slope == 0.0 || slope == 1.0) || inter != 0.0) ? 1 : 0;
+  return Scale{slope == 0.0 ? 1.0 : slope, inter, on};
+}
+
+// a voxel as read_nifti hands it on: fp64 raw * slope + inter when scaling applies (product
+// and sum rounded separately), else the raw value itself
+template <typename T> __device__ __forceinline__ double scaled(T raw, const Scale& sc) {
+  return (double)raw * sc.slope + sc.inter;
+}
+// the image sample ProstateDataset.__getitem__ resamples: that value as fp32
+template <typename T> __device__ __forceinline__ float image_value(T raw, const Scale& sc) {
+  return sc.on ? (float)scaled(raw, sc) : (float)raw;
+}
+
+struct Tap {
+  long lo, hi;  // clamped neighbours
+  double w;
+  bool outside;
+};
+__device__ __forceinline__ Tap linear_tap(const Axis& a, int i) {
+  Tap t;
+  if (a.ident) {
+    t.lo = t.hi = i;
+    t.w = 0.0;
+    t.outside = false;
+    return t;
+  }
+  const double c = (double)i * a.ratio;
+  const double f = floor(c);
+  const long i0 = (int)f;  // c < n_in <= INT_MAX
+  t.w = c - f;
+  t.lo = i0 < a.n_in - 1 ? i0 : a.n_in - 1;  // c >= 0: no lower clamp can bind
+  t.hi = i0 + 1 < a.n_in - 1 ? i0 + 1 : a.n_in - 1;
+  t.outside = !(c < a.edge);
+  return t;
+}
+__device__ __forceinline__ double lerp(double a, double b, double w) { return a * (1.0 - w) + b * w; }
+
+template <typename T>
+__global__ void __launch_bounds__(TPB) resample_linear_kernel(const T* __restrict__ src, float* __restrict__ out,
+                                                              Axis ad, Axis ah, Axis aw, Scale sc) {
+  const long HW = (long)ah.n_out * aw.n_out;
+  const long total = (long)ad.n_out * HW;
+  const long sH = aw.n_in, sD = (long)ah.n_in * aw.n_in;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int d = (int)(i / HW);
+    const long r = i - d * HW;
+    const int h = (int)(r / aw.n_out), w = (int)(r - (long)h * aw.n_out);
+    const Tap td = linear_tap(ad, d), th = linear_tap(ah, h), tw = linear_tap(aw, w);
+    float res = 0.f;
+    if (!(td.outside || th.outside || tw.outside)) {
+      double vh[2];
+#pragma unroll
+      for (int jw = 0; jw < 2; ++jw) {
+        const long xw = jw ? tw.hi : tw.lo;
+        double vd[2];
+#pragma unroll
+        for (int jh = 0; jh < 2; ++jh) {
+          const long xh = (jh ? th.hi : th.lo) * sH + xw;
+          const double a = (double)image_value(src[td.lo * sD + xh], sc);
+          vd[jh] = ad.ident ? a : lerp(a, (double)image_value(src[td.hi * sD + xh], sc), td.w);
+        }
+        vh[jw] = ah.ident ? vd[0] : lerp(vd[0], vd[1], th.w);
+      }
+      res = (float)(aw.ident ? vh[0] : lerp(vh[0], vh[1], tw.w));
+    }
+    out[i] = res;
+  }
+}
+
+// nearest index of one axis (rounded half up); -1: past the input (the output is 0 there)
+__device__ __forceinline__ long nearest_index(const Axis& a, int i) {
+  if (a.ident) return i;
+  const long k = (int)floor((double)i * a.ratio + 0.5);  // <= n_in <= INT_MAX
+  return k < a.n_in ? k : -1;
+}
+
+// round32: data.resample's result is fp32 before the loader's `> 0`; a volume already of the
+// target shape is not resampled and is compared as read (ProstateDataset.__getitem__)
+template <typename T>
+__global__ void __launch_bounds__(TPB) resample_label_kernel(const T* __restrict__ src, float* __restrict__ out,
+                                                             Axis ad, Axis ah, Axis aw, Scale sc, int round32) {
+  const long HW = (long)ah.n_out * aw.n_out;
+  const long total = (long)ad.n_out * HW;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int d = (int)(i / HW);
+    const long r = i - d * HW;
+    const int h = (int)(r / aw.n_out), w = (int)(r - (long)h * aw.n_out);
+    const long kd = nearest_index(ad, d), kh = nearest_index(ah, h), kw = nearest_index(aw, w);
+    float res = 0.f;
+    if (kd >= 0 && kh >= 0 && kw >= 0) {
+      const T raw = src[(kd * ah.n_in + kh) * aw.n_in + kw];
+      bool fg;
+      if (sc.on) {
+        const double v = scaled(raw, sc);
+        fg = round32 ? (float)v > 0.f : v > 0.0;
+      } else if constexpr (sizeof(T) == 8 && std::is_floating_point<T>::value) {
+        fg = round32 ? (float)raw > 0.f : raw > 0.0;
+      } else {
+        fg = raw > (T)0;  // every other type keeps its sign through the fp32 rounding
+      }
+      res = fg ? 1.f : 0.f;
+    }
+    out[i] = res;
+  }
+}
+
+template <typename T>
+int launch(bool label, const void* src, float* out, const Axis& ad, const Axis& ah, const Axis& aw, const Scale& sc,
+           hipStream_t s) {
+  if (((uintptr_t)src) % alignof(T) != 0) return -1;
+  const long total = (long)ad.n_out * ah.n_out * aw.n_out;
+  const int grid = grid_for(total, TPB);
+  if (label)
+    hipLaunchKernelGGL(resample_label_kernel<T>, dim3(grid), dim3(TPB), 0, s, (const T*)src, out, ad, ah, aw, sc,
+                       (ad.ident && ah.ident && aw.ident) ? 0 : 1);
+  else
+    hipLaunchKernelGGL(resample_linear_kernel<T>, dim3(grid), dim3(TPB), 0, s, (const T*)src, out, ad, ah, aw, sc);
+  PCMS_CHECK_LAUNCH();
+}
+
+int resample(bool label, const void* src, int code, int Di, int Hi, int Wi, double slope, double inter, float* out,
+             int D, int H, int W, hipStream_t s) {
+  if (src == nullptr || out == nullptr) return -1;
+  if (Di < 1 || Hi < 1 || Wi < 1 || D < 1 || H < 1 || W < 1) return -1;
+  if (((uintptr_t)out) % alignof(float) != 0) return -1;
+  const Axis ad = make_axis(Di, D), ah = make_axis(Hi, H), aw = make_axis(Wi, W);
+  const Scale sc = make_scale(slope, inter);
+  switch (code) {  // NIfTI-1 datatype codes (data._NIFTI_DTYPES)
+    case 2: return launch<uint8_t>(label, src, out, ad, ah, aw, sc, s);
+    case 4: return launch<int16_t>(label, src, out, ad, ah, aw, sc, s);
+    case 8: return launch<int32_t>(label, src, out, ad, ah, aw, sc, s);
+    case 16: return launch<float>(label, src, out, ad, ah, aw, sc, s);
+    case 64: return launch<double>(label, src, out, ad, ah, aw, sc, s);
+    case 256: return launch<int8_t>(label, src, out, ad, ah, aw, sc, s);
+    case 512: return launch<uint16_t>(label, src, out, ad, ah, aw, sc, s);
+    case 768: return launch<uint32_t>(label, src, out, ad, ah, aw, sc, s);
+    case 1024: return launch<int64_t>(label, src, out, ad, ah, aw, sc, s);
+    case 1280: return launch<uint64_t>(label, src, out, ad, ah, aw, sc, s);
+    default: return -1;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int pcms_resample_linear(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope, double scl_inter,
+                         float* out, int D, int H, int W, hipStream_t s) {
+  return resample(false, src, datatype, Di, Hi, Wi, scl_slope, scl_inter, out, D, H, W, s);
+}
+
+int pcms_resample_label(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope, double scl_inter,
+                        float* out, int D, int H, int W, hipStream_t s) {
+  return resample(true, src, datatype, Di, Hi, Wi, scl_slope, scl_inter, out, D, H, W, s);
+}
+
+}  // extern "C"

@@ -21,11 +21,16 @@ Dataset semantics follow script/data_loader.py:
     (nearest) and binarised ``> 0`` (:240-283, :379-409);
   * batches ``{'image': (N, M, D, H, W) f32, 'label': (N, 1, D, H, W) f32, 'case_id': [..]}``
     from a ``DataLoader`` with ``pin_memory`` (:421-466).
+``device_resample=True`` (dataset and loader) moves the resampling to the GPU: samples carry the
+files' undecoded first volumes (``read_nifti_raw`` -> ``RawVolume``) and ``assemble_batch``
+uploads the bytes and runs ``resample_device`` (libpcms_hip's pcms_resample_linear / _label, the
+arithmetic of ``resample`` restated per voxel) into the batch: the same batches bit for bit.
 The reference's SimpleITK ``SetSize`` takes (x, y, z), so its non-cubic outputs come out
 axis-reversed; here ``target_size`` is (D, H, W) as documented (:41).
 """
 from __future__ import annotations
 
+import dataclasses
 import glob
 import gzip
 import os
@@ -93,6 +98,53 @@ def read_nifti(path: str) -> np.ndarray:
     return np.ascontiguousarray(arr)
 
 
+@dataclasses.dataclass
+class RawVolume:
+    """The first 3-D volume of a NIfTI file as stored: its voxel bytes (1-D ``torch.uint8``,
+    little endian), the NIfTI datatype code, the (D, H, W) shape and the header's scaling --
+    what ``resample_device`` needs to form ``read_nifti``'s values on the GPU."""
+    data: torch.Tensor
+    code: int
+    shape: Tuple[int, int, int]
+    slope: float
+    inter: float
+
+    def pin_memory(self) -> "RawVolume":  # DataLoader(pin_memory=True) calls this on custom types
+        return dataclasses.replace(self, data=self.data.pin_memory())
+
+    def to(self, device, non_blocking: bool = False) -> "RawVolume":
+        return dataclasses.replace(self, data=self.data.to(device, non_blocking=non_blocking))
+
+    def numpy(self) -> np.ndarray:
+        """The volume as ``read_nifti`` returns it (host bytes only)."""
+        dt = np.dtype(_NIFTI_DTYPES[self.code]).newbyteorder("<")
+        arr = np.frombuffer(self.data.numpy().tobytes(), dtype=dt).reshape(self.shape)
+        if self.slope not in (0.0, 1.0) or self.inter != 0.0:
+            arr = arr.astype(np.float64) * (self.slope if self.slope != 0.0 else 1.0) + self.inter
+        return np.ascontiguousarray(arr)
+
+
+def read_nifti_raw(path: str) -> RawVolume:
+    """The first 3-D volume of ``path`` undecoded (a 4-D file contributes volume 0, as
+    ``ProstateDataset._first_volume`` takes it); a big-endian file is byte-swapped here."""
+    h = read_nifti_header(path)
+    if len(h["shape_xyz"]) not in (3, 4):
+        raise ValueError(f"unsupported image dimensions: {h['shape_xyz'][::-1]}")
+    dt = np.dtype(_NIFTI_DTYPES[h["datatype"]]).newbyteorder(h["endian"])
+    shape = tuple(int(v) for v in h["shape_xyz"][:3][::-1])
+    nbytes = int(np.prod(shape)) * dt.itemsize
+    with _open(path) as f:
+        f.read(max(h["vox_offset"], 352))
+        buf = f.read(nbytes)
+    if len(buf) < nbytes:
+        raise ValueError(f"{path}: truncated voxel data")
+    arr = np.frombuffer(buf, dtype=dt)
+    if h["endian"] == ">":
+        arr = arr.astype(dt.newbyteorder("<"))
+    data = torch.from_numpy(arr.view(np.uint8).copy())
+    return RawVolume(data, int(h["datatype"]), shape, h["scl_slope"], h["scl_inter"])
+
+
 def write_nifti(path: str, arr_zyx: np.ndarray, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> None:
     """Minimal NIfTI-1 writer (single file, little endian) for tests and synthetic data."""
     codes = {np.dtype(v): k for k, v in _NIFTI_DTYPES.items()}
@@ -155,6 +207,87 @@ def resample(vol: np.ndarray, target: Tuple[int, int, int], nearest: bool = Fals
     return out.astype(np.float32)
 
 
+def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool = False,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``resample`` of a volume whose bytes are on the GPU, on the current stream: the linear
+    form equals ``resample(vol.astype(float32), target)`` bit for bit, ``nearest=True`` gives
+    the binarised label ``resample(vol, target, nearest=True) > 0`` as fp32 {0, 1} (for a
+    volume already of the target shape, ``vol > 0``), as ``ProstateDataset.__getitem__`` forms
+    them.  Fills ``out`` (a contiguous fp32 (D, H, W) device tensor, e.g. one channel of a
+    batch) or returns a new one.  There is no CPU form: host bytes raise."""
+    from ._lib import call
+    target = tuple(int(v) for v in target)
+    if raw.data.device.type != "cuda":
+        raise RuntimeError("resample_device needs the volume's bytes on a GPU (RawVolume.to(device)); "
+                           "pcms_amd has no CPU fallback -- use data.resample on the host")
+    if raw.data.dtype != torch.uint8 or not raw.data.is_contiguous():
+        raise ValueError("RawVolume.data must be a contiguous uint8 tensor")
+    itemsize = np.dtype(_NIFTI_DTYPES[raw.code]).itemsize
+    if raw.data.numel() != int(np.prod(raw.shape)) * itemsize:
+        raise ValueError(f"RawVolume holds {raw.data.numel()} bytes, shape {raw.shape} of datatype {raw.code} "
+                         f"needs {int(np.prod(raw.shape)) * itemsize}")
+    if out is None:
+        out = torch.empty(target, dtype=torch.float32, device=raw.data.device)
+    elif (tuple(out.shape) != target or out.dtype != torch.float32 or not out.is_contiguous()
+          or out.device != raw.data.device):
+        raise ValueError(f"out must be a contiguous fp32 {target} tensor on {raw.data.device}")
+    call("pcms_resample_label" if nearest else "pcms_resample_linear", raw.data, int(raw.code), *raw.shape,
+         float(raw.slope), float(raw.inter), out, *target)
+    return out
+
+
+def is_raw_batch(batch) -> bool:
+    return isinstance(batch, dict) and "raw_images" in batch
+
+
+def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] = None, device=None) -> Dict:
+    """A ``device_resample`` loader's batch -> ``{'image': (N, M, D, H, W) f32, 'label':
+    (N, 1, D, H, W) f32, 'case_id': [...]}`` on ``device``, equal to the default loader's
+    batch: each volume's bytes go up from pinned memory in their native type and one resample
+    launch writes its channel plane; ``None`` channels (zero_fill) are zeroed.  Everything is
+    enqueued on the current stream.  ``target_size`` defaults to the one the loader recorded."""
+    target = tuple(int(v) for v in (target_size if target_size is not None else raw_batch["target_size"]))
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda":
+        raise RuntimeError(f"a device_resample batch can only be assembled on a GPU, not on '{device}': "
+                           "pcms_amd has no CPU resampling kernel (use the default loader there)")
+    images, labels = raw_batch["raw_images"], raw_batch["raw_label"]
+    n, m = len(images), len(images[0])
+    with torch.cuda.device(device):
+        image = torch.empty((n, m) + target, dtype=torch.float32, device=device)
+        label = torch.empty((n, 1) + target, dtype=torch.float32, device=device)
+
+        def up(raw):
+            return raw if raw.data.device.type == "cuda" else raw.pin_memory().to(device, non_blocking=True)
+
+        for i in range(n):
+            for c, raw in enumerate(images[i]):
+                if raw is None:
+                    image[i, c].zero_()
+                else:
+                    resample_device(up(raw), target, out=image[i, c])
+            resample_device(up(labels[i]), target, nearest=True, out=label[i, 0])
+    return {"image": image, "label": label, "case_id": list(raw_batch["case_id"])}
+
+
+def device_batch(batch: Dict, device) -> Dict:
+    """What every consumer of a loader's batch calls first: a ``device_resample`` batch is
+    assembled on ``device`` (``assemble_batch``); any other batch passes through untouched."""
+    return assemble_batch(batch, None, device) if is_raw_batch(batch) else batch
+
+
+class _CollateRaw:
+    """Collate of ``device_resample`` samples: raw shapes differ between cases and modalities,
+    so the descriptors stay in lists (nothing is stacked); the target size rides along."""
+
+    def __init__(self, target_size):
+        self.target_size = tuple(int(v) for v in target_size)
+
+    def __call__(self, samples: List[Dict]) -> Dict:
+        return {"raw_images": [s["raw_images"] for s in samples], "raw_label": [s["raw_label"] for s in samples],
+                "case_id": [s["case_id"] for s in samples], "target_size": self.target_size}
+
+
 def _find(base: str, case_id: str) -> Optional[str]:
     for ext in (".nii", ".nii.gz"):
         p = os.path.join(base, case_id + ext)
@@ -168,7 +301,7 @@ class ProstateDataset(Dataset):
 
     def __init__(self, data_dir: str, modalities: Optional[List[str]] = None, missing_strategy: str = "zero_fill",
                  target_size: Tuple[int, int, int] = (128, 128, 128), is_training: bool = True,
-                 data_type: str = "BPH"):
+                 data_type: str = "BPH", device_resample: bool = False):
         if missing_strategy not in ("zero_fill", "skip", "duplicate"):
             raise ValueError(f"unsupported missing-modality strategy: {missing_strategy}")
         self.data_dir = data_dir
@@ -177,6 +310,7 @@ class ProstateDataset(Dataset):
         self.target_size = tuple(int(v) for v in target_size)
         self.is_training = is_training
         self.data_type = data_type
+        self.device_resample = bool(device_resample)
         self.case_list = self._filter_cases(self._get_case_list())
 
     def _root(self, *parts) -> str:
@@ -236,6 +370,11 @@ class ProstateDataset(Dataset):
 
     def __getitem__(self, idx: int) -> Dict:
         case = self.case_list[idx]
+        if self.device_resample:
+            # undecoded volumes for assemble_batch (None: a zero_fill channel); no numpy resampling
+            files = case["modality_files"]
+            return {"raw_images": [read_nifti_raw(files[m]) if m in files else None for m in self.modalities],
+                    "raw_label": read_nifti_raw(case["label_path"]), "case_id": case["case_id"]}
         chans = []
         for m in self.modalities:
             p = case["modality_files"].get(m)
@@ -257,12 +396,16 @@ class ProstateDataset(Dataset):
 def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, modalities=None,
                    missing_strategy: str = "zero_fill", target_size=(128, 128, 128), num_workers: int = 0,
                    is_training: bool = True, data_type: str = "BPH", indices=None, rank: int = 0,
-                   world_size: int = 1) -> DataLoader:
+                   world_size: int = 1, device_resample: bool = False) -> DataLoader:
     """script/data_loader.py:421-466 (pinned host batches; Trainer stages them to the GPU on
     a copy stream one batch ahead).  ``world_size > 1``: each rank iterates its own
-    DistributedSampler shard (call ``loader.sampler.set_epoch(epoch)`` every epoch)."""
+    DistributedSampler shard (call ``loader.sampler.set_epoch(epoch)`` every epoch).
+    ``device_resample``: the batches carry the files' undecoded volumes (``RawVolume`` lists,
+    same cases in the same order); ``assemble_batch`` resamples them on the GPU."""
     ds = ProstateDataset(data_dir, modalities=modalities, missing_strategy=missing_strategy,
-                         target_size=target_size, is_training=is_training, data_type=data_type)
+                         target_size=target_size, is_training=is_training, data_type=data_type,
+                         device_resample=device_resample)
+    collate = _CollateRaw(target_size) if device_resample else None
     if indices is not None:
         ds = torch.utils.data.Subset(ds, indices)
     sampler = None
@@ -271,12 +414,12 @@ def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, mod
         # padding, no duplicates: the (sum, count) of per-batch losses over ranks is the
         # single-process mean)
         return DataLoader(ds, batch_sampler=BatchShard(len(ds), batch_size, rank, world_size),
-                          num_workers=num_workers, pin_memory=torch.cuda.is_available())
+                          num_workers=num_workers, pin_memory=torch.cuda.is_available(), collate_fn=collate)
     if world_size > 1:
         sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=world_size, rank=rank,
                                                                   shuffle=shuffle)
     return DataLoader(ds, batch_size=batch_size, shuffle=shuffle and sampler is None, sampler=sampler,
-                      num_workers=num_workers, pin_memory=torch.cuda.is_available())
+                      num_workers=num_workers, pin_memory=torch.cuda.is_available(), collate_fn=collate)
 
 
 class BatchShard(torch.utils.data.Sampler):

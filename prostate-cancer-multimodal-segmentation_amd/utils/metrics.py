@@ -14,6 +14,8 @@ from typing import Dict, Iterable, List, Optional
 
 import torch
 
+from ..data import device_batch
+
 
 def calculate_dice_score(pred: torch.Tensor, target: torch.Tensor) -> float:
     """2|X∩Y| / (|X| + |Y| + 1e-8) over all voxels (validate_model.py:24-50)."""
@@ -38,6 +40,7 @@ def evaluate(model, loader: Iterable, threshold: float = 0.5, device=None) -> Di
     model.eval()
     cases: List[Dict] = []
     for batch in loader:
+        batch = device_batch(batch, device)
         x = batch["image"].to(device, non_blocking=True)
         y = batch["label"].to(device, non_blocking=True)
         mask = model.inference(x, threshold=threshold)

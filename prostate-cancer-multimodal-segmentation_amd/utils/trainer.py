@@ -20,8 +20,10 @@ BatchNorm statistics and the global Dice stay per replica (plain BatchNorm3d, SU
 
 Config keys follow utils/trainer.py:40-49 (``device``, ``learning_rate``, ``batch_size``,
 ``num_epochs``, ``save_dir``, ``validation`` ...) plus ``loss`` ('dice' | 'bce_dice'),
-``precision`` ('bf16' | 'fp32'), ``checkpoint_decoder``, and the step variants of the other
-reference trainers:
+``precision`` ('bf16' | 'fp32'), ``checkpoint_decoder``, ``device_resample`` (the ``data_dir``
+loaders hand over the files' undecoded volumes and ``data.assemble_batch`` resamples them on
+the GPU, on the copy stream beside the previous step; same batches bit for bit), and the step
+variants of the other reference trainers:
   ``max_grad_norm``  clip_grad_norm_(max_norm) before Adam (train_bph.py:166,
                      train_bph_cv.py:311 use 1.0): one fused norm pass, the clip coefficient
                      folded into the Adam kernel;
@@ -42,6 +44,7 @@ import torch.distributed as dist
 
 from .._lib import call, query
 from ..amp import GradScaler
+from ..data import assemble_batch, device_batch, is_raw_batch
 from ..dp import GradSync
 from ..models.unet3d import UNet3D
 from ..optim import FlatAdam
@@ -107,7 +110,8 @@ class BaseTrainer:
                                                                self.config.get("missing_strategy", "zero_fill")),
                               target_size=tuple(self.config.get("target_size", (128, 128, 128))),
                               is_training=mode == "train", data_type=self.config.get("data_type", "BPH"),
-                              rank=self.rank, world_size=self.world_size)
+                              rank=self.rank, world_size=self.world_size,
+                              device_resample=bool(self.config.get("device_resample", False)))
 
     def _broadcast_params(self):
         eng = self.model.engine()
@@ -138,6 +142,7 @@ class BaseTrainer:
     def step_async(self, batch) -> torch.Tensor:
         """One training step; returns the loss as a device tensor (no host sync unless the
         AMP variant has to decide whether to skip the update)."""
+        batch = device_batch(batch, self.device)
         images = batch["image"].to(self.device, non_blocking=True)
         labels = batch["label"].to(self.device, non_blocking=True)
         if not self.model.training:  # (the engine follows UNet3D.training only)
@@ -184,7 +189,8 @@ class BaseTrainer:
         return loss.detach()
 
     def _prefetched(self, loader):
-        """Yield batches whose H2D copy ran on a side stream while the previous step ran."""
+        """Yield batches whose H2D copy (and, for a ``device_resample`` loader's batch, the
+        resampling of its volumes) ran on a side stream while the previous step ran."""
         if self.device.type != "cuda":
             yield from loader
             return
@@ -194,9 +200,12 @@ class BaseTrainer:
         nxt = None
         for batch in loader:
             with torch.cuda.stream(cs):
-                staged = {k: (v.pin_memory().to(self.device, non_blocking=True)
-                              if torch.is_tensor(v) and v.device.type == "cpu" else v)
-                          for k, v in batch.items()}
+                if is_raw_batch(batch):
+                    staged = assemble_batch(batch, None, self.device)
+                else:
+                    staged = {k: (v.pin_memory().to(self.device, non_blocking=True)
+                                  if torch.is_tensor(v) and v.device.type == "cpu" else v)
+                              for k, v in batch.items()}
                 ev = torch.cuda.Event()
                 ev.record(cs)
             if nxt is not None:
@@ -225,6 +234,7 @@ class BaseTrainer:
         total, n = 0.0, 0
         with torch.no_grad():
             for batch in self.val_loader:
+                batch = device_batch(batch, self.device)
                 out = self.model(batch["image"].to(self.device))
                 total += self.criterion(out, batch["label"].to(self.device)).item()
                 n += 1
