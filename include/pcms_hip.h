@@ -431,6 +431,24 @@ int pcms_resample_linear(const void* src, int datatype, int Di, int Hi, int Wi, 
  * volume already has the target shape (ProstateDataset compares that one as read).        */
 int pcms_resample_label(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope, double scl_inter,
                         float* out, int D, int H, int W, hipStream_t s);
+/* Training-time augmentation (data.resample_affine on the device, bit for bit): the same
+ * gather under a 3x4 affine.  affine12: twelve HOST doubles, row-major A[3][3] then t[3],
+ * copied into the kernel arguments.  Output index (d, h, w) samples source axis a at
+ * c_a = ((A[a][0] d + A[a][1] h) + A[a][2] w) + t[a] in fp64, every product and sum rounded on
+ * its own.  Linear: inside iff -0.5 <= c_a < n_a - 0.5 on all axes (decided on the doubles);
+ * there i0 = floor(c), w = c - i0, neighbours i0 and i0 + 1 each clamped to [0, n - 1], the 8
+ * corners lerped a (1 - w) + b w over D, then H, then W, one rounding to fp32, then -- unless
+ * gain == 1 and bias == 0 -- fl32(fl32(r * gain) + bias); outside voxels are 0.  With
+ * A = diag(n_in / n_out), t = 0 this is pcms_resample_linear's result.  Rejects what the plain
+ * entry points reject, a NULL affine12 and any non-finite affine12 / gain / bias.          */
+int pcms_resample_affine_linear(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
+                                double scl_inter, const double* affine12, float gain, float bias, float* out, int D,
+                                int H, int W, hipStream_t s);
+/* The label form: k_a = floor(c_a + 0.5); 0 where any k_a < 0 or k_a >= n_a, else
+ * ((float)value > 0 ? 1 : 0), the decoded value always rounded to fp32 first.             */
+int pcms_resample_affine_label(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
+                               double scl_inter, const double* affine12, float* out, int D, int H, int W,
+                               hipStream_t s);
 
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,

@@ -117,6 +117,8 @@ SIGNATURES = {
     "pcms_unpack_output": "ippiiils",
     "pcms_resample_linear": "piiiiddpiiis",
     "pcms_resample_label": "piiiiddpiiis",
+    "pcms_resample_affine_linear": "piiiiddpffpiiis",  # affine12: a host pointer (ctypes.addressof)
+    "pcms_resample_affine_label": "piiiiddppiiis",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

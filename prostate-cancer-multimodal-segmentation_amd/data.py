@@ -25,11 +25,16 @@ Dataset semantics follow script/data_loader.py:
 files' undecoded first volumes (``read_nifti_raw`` -> ``RawVolume``) and ``assemble_batch``
 uploads the bytes and runs ``resample_device`` (libpcms_hip's pcms_resample_linear / _label, the
 arithmetic of ``resample`` restated per voxel) into the batch: the same batches bit for bit.
+``augment=...`` (dataset, loader, ``Trainer`` config) turns on training-time augmentation: one
+3x4 affine per case and epoch (``draw_transform``: flips, rotations, zoom, shift; gain / bias per
+modality) under which every volume of the case is resampled -- ``resample_affine`` on the host,
+pcms_resample_affine_linear / _label in ``assemble_batch`` -- again the same batches bit for bit.
 The reference's SimpleITK ``SetSize`` takes (x, y, z), so its non-cubic outputs come out
 axis-reversed; here ``target_size`` is (D, H, W) as documented (:41).
 """
 from __future__ import annotations
 
+import ctypes
 import dataclasses
 import glob
 import gzip
@@ -207,14 +212,177 @@ def resample(vol: np.ndarray, target: Tuple[int, int, int], nearest: bool = Fals
     return out.astype(np.float32)
 
 
+def resample_affine(vol: np.ndarray, target: Tuple[int, int, int], A, t, nearest: bool = False,
+                    gain: float = 1.0, bias: float = 0.0) -> np.ndarray:
+    """``resample`` under a full affine (training-time augmentation): output index (d, h, w)
+    samples source axis a at ``c_a = ((A[a][0]*d + A[a][1]*h) + A[a][2]*w) + t[a]`` -- fp64,
+    every product and sum a numpy operation of its own, in this order.  A gather over the
+    output grid; libpcms_hip's pcms_resample_affine_linear / _label restate it per voxel and
+    are compared with it on the fp32 bits.
+
+    Linear: inside iff ``-0.5 <= c_a < n_a - 0.5`` on all three axes (ITK's buffer rule, as
+    ``_axis_linear``); there ``i0 = floor(c)``, ``w = c - i0``, neighbours ``i0`` and ``i0 + 1``
+    each clamped to ``[0, n - 1]``, the 8 corners lerped ``a*(1-w) + b*w`` along D, then H, then
+    W, rounded once to fp32; unless ``gain == 1 and bias == 0`` an inside voxel then becomes
+    ``fl32(fl32(r*gain) + bias)`` (``gain`` / ``bias`` as fp32).  Outside voxels are 0.
+    ``nearest``: ``k_a = floor(c_a + 0.5)``, 0 where any ``k_a`` is outside ``[0, n_a)``, else the
+    voxel's value as fp32 (the loader binarises it ``> 0``).
+    With ``A = diag(n_in / n_out)``, ``t = 0`` both forms equal ``resample`` bit for bit."""
+    A = np.asarray(A, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    D, H, W = (int(v) for v in target)
+    n_in = vol.shape
+    grid = (np.arange(D, dtype=np.float64).reshape(D, 1, 1), np.arange(H, dtype=np.float64).reshape(1, H, 1),
+            np.arange(W, dtype=np.float64).reshape(1, 1, W))
+    with np.errstate(over="ignore", invalid="ignore"):  # a far-out coordinate may overflow: it is outside
+        c = [((A[a, 0] * grid[0] + A[a, 1] * grid[1]) + A[a, 2] * grid[2]) + t[a] for a in range(3)]
+        if nearest:
+            k = [np.floor(c[a] + 0.5) for a in range(3)]
+            inside = np.ones((D, H, W), dtype=bool)
+            for a in range(3):
+                inside &= (k[a] >= 0.0) & (k[a] < float(n_in[a]))
+            idx = [np.where(inside, k[a], 0.0).astype(np.int64) for a in range(3)]
+            return np.where(inside, vol[idx[0], idx[1], idx[2]], 0).astype(np.float32)
+        inside = np.ones((D, H, W), dtype=bool)
+        for a in range(3):
+            inside &= (c[a] >= -0.5) & (c[a] < n_in[a] - 0.5)
+    lo, hi, w = [], [], []
+    for a in range(3):
+        ca = np.where(inside, c[a], 0.0)
+        i0 = np.floor(ca).astype(np.int64)
+        w.append(ca - i0)
+        lo.append(np.clip(i0, 0, n_in[a] - 1))
+        hi.append(np.clip(i0 + 1, 0, n_in[a] - 1))
+    v = vol.astype(np.float64)
+    vh = []
+    for xw in (lo[2], hi[2]):
+        vd = [v[lo[0], xh, xw] * (1.0 - w[0]) + v[hi[0], xh, xw] * w[0] for xh in (lo[1], hi[1])]
+        vh.append(vd[0] * (1.0 - w[1]) + vd[1] * w[1])
+    out = (vh[0] * (1.0 - w[2]) + vh[1] * w[2]).astype(np.float32)
+    gain, bias = np.float32(gain), np.float32(bias)
+    if not (gain == 1.0 and bias == 0.0):
+        out = out * gain + bias  # two fp32 operations
+    return np.where(inside, out, np.float32(0.0))
+
+
+@dataclasses.dataclass
+class Augment:
+    """Training-time augmentation settings (also accepted as a plain dict of these fields).
+    The defaults are all identity: nothing is varied and the transform is exactly the plain
+    resampler's."""
+    flip_prob: Tuple[float, float, float] = (0.0, 0.0, 0.0)    # per axis (D, H, W)
+    rotate_deg: Tuple[float, float, float] = (0.0, 0.0, 0.0)   # max |angle| about the D, H, W axes
+    zoom: Tuple[float, float] = (1.0, 1.0)                     # (lo, hi)
+    shift_frac: Tuple[float, float, float] = (0.0, 0.0, 0.0)   # max |shift| per axis / output extent
+    gain: Tuple[float, float] = (1.0, 1.0)                     # (lo, hi), drawn per modality
+    bias: Tuple[float, float] = (0.0, 0.0)                     # (lo, hi), drawn per modality
+
+    @staticmethod
+    def of(aug) -> Optional["Augment"]:
+        if aug is None or isinstance(aug, Augment):
+            return aug
+        return Augment(**dict(aug))
+
+    def __post_init__(self):
+        for name, n in (("flip_prob", 3), ("rotate_deg", 3), ("shift_frac", 3), ("zoom", 2), ("gain", 2), ("bias", 2)):
+            v = getattr(self, name)
+            v = (float(v),) * n if np.isscalar(v) and n == 3 else tuple(float(x) for x in v)
+            if len(v) != n or not all(np.isfinite(v)):
+                raise ValueError(f"Augment.{name} must hold {n} finite numbers, got {getattr(self, name)!r}")
+            setattr(self, name, v)
+        if not self.zoom[0] > 0.0:
+            raise ValueError(f"Augment.zoom must be positive, got {self.zoom!r}")
+
+
+def _matmul3(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """3x3 product with a fixed order of operations (no BLAS: the same doubles everywhere)."""
+    return np.array([[(a[i, 0] * b[0, j] + a[i, 1] * b[1, j]) + a[i, 2] * b[2, j] for j in range(3)] for i in range(3)])
+
+
+def compose_transform(flips=(False, False, False), rotate_deg=(0.0, 0.0, 0.0), zoom: float = 1.0) -> np.ndarray:
+    """The geometric part ``L`` of a transform, in the output grid's index space:
+    ``M = R_D(td) . R_H(th) . R_W(tw)`` (rotations about the D, H and W axes),
+    ``L = F . M^T / zoom`` with ``F = diag(+-1)`` holding the flips."""
+    td, th, tw = (float(np.deg2rad(a)) for a in rotate_deg)
+    c, s = np.cos, np.sin
+    rd = np.array([[1.0, 0.0, 0.0], [0.0, c(td), -s(td)], [0.0, s(td), c(td)]])
+    rh = np.array([[c(th), 0.0, s(th)], [0.0, 1.0, 0.0], [-s(th), 0.0, c(th)]])
+    rw = np.array([[c(tw), -s(tw), 0.0], [s(tw), c(tw), 0.0], [0.0, 0.0, 1.0]])
+    m = _matmul3(_matmul3(rd, rh), rw)
+    f = np.array([-1.0 if b else 1.0 for b in flips])
+    return (f[:, None] * m.T) / float(zoom) + 0.0  # + 0.0: no negative zeros
+
+
+def volume_affine(L, shift, n_in, n_out) -> Tuple[np.ndarray, np.ndarray]:
+    """One volume's ``(A, t)`` of a case's transform: with ``S = diag(n_in / n_out)`` and the
+    output grid's centre ``C = (n_out - 1) / 2``, ``A = S.L`` and ``t = S.(C - L.C - shift)``
+    (``shift`` in output voxels): every volume of a case sees one geometry in output space."""
+    L = np.asarray(L, dtype=np.float64).reshape(3, 3)
+    shift = np.asarray(shift, dtype=np.float64).reshape(3)
+    S = np.array([float(i) / float(o) for i, o in zip(n_in, n_out)])  # numpy's n_in / n_out, as resample
+    C = np.array([(float(o) - 1.0) / 2.0 for o in n_out])
+    LC = np.array([(L[a, 0] * C[0] + L[a, 1] * C[1]) + L[a, 2] * C[2] for a in range(3)])
+    return S[:, None] * L + 0.0, S * ((C - LC) - shift) + 0.0
+
+
+@dataclasses.dataclass
+class Transform:
+    """One case's drawn transform: ``L`` (3x3) and ``shift_frac`` (the shift as a fraction of
+    the output extent, per axis) shared by every volume of the case, ``gain`` / ``bias`` per
+    modality."""
+    L: np.ndarray
+    shift_frac: np.ndarray
+    gain: Tuple[float, ...]
+    bias: Tuple[float, ...]
+
+    def affine(self, n_in, n_out) -> Tuple[np.ndarray, np.ndarray]:
+        n_out = tuple(int(v) for v in n_out)
+        return volume_affine(self.L, self.shift_frac * np.array(n_out, dtype=np.float64), n_in, n_out)
+
+    def affine12(self, n_in, n_out) -> Tuple[float, ...]:
+        """``affine`` as the twelve doubles the C entry points take: row-major A, then t."""
+        A, t = self.affine(n_in, n_out)
+        return tuple(float(v) for v in A.reshape(-1)) + tuple(float(v) for v in t)
+
+
+def draw_transform(aug, seed: int, epoch: int, case_number: int,
+                   n_modalities: int = len(DEFAULT_MODALITIES)) -> Transform:
+    """The transform of case ``case_number`` (its index in ``ProstateDataset.case_list`` --
+    not a position in a Subset, a rank's shard or a worker) in ``epoch``: a function of
+    ``(seed, epoch, case_number)`` alone, so loader topology and a resume do not change it.
+
+    Stream: ``np.random.default_rng([seed, epoch, case_number])``; every draw is one
+    ``rng.random()`` (u in [0, 1)), always taken, in this order:
+      1-3    flips of D, H, W: flipped iff ``u < flip_prob[a]``;
+      4-6    angles about D, H, W: ``rotate_deg[a] * (2u - 1)`` degrees;
+      7      zoom: ``lo + (hi - lo) * u``;
+      8-10   shifts of D, H, W: ``shift_frac[a] * (2u - 1)`` of the output extent;
+      then per modality m = 0 .. n_modalities - 1:  gain_m, bias_m: ``lo + (hi - lo) * u`` each."""
+    aug = Augment.of(aug)
+    rng = np.random.default_rng([int(seed), int(epoch), int(case_number)])
+    flips = [rng.random() < p for p in aug.flip_prob]
+    angles = [m * (2.0 * rng.random() - 1.0) for m in aug.rotate_deg]
+    zoom = aug.zoom[0] + (aug.zoom[1] - aug.zoom[0]) * rng.random()
+    shift = np.array([m * (2.0 * rng.random() - 1.0) for m in aug.shift_frac]) + 0.0
+    gain, bias = [], []
+    for _ in range(int(n_modalities)):
+        gain.append(float(aug.gain[0] + (aug.gain[1] - aug.gain[0]) * rng.random()))
+        bias.append(float(aug.bias[0] + (aug.bias[1] - aug.bias[0]) * rng.random()))
+    return Transform(compose_transform(flips, angles, zoom), shift, tuple(gain), tuple(bias))
+
+
 def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool = False,
-                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    out: Optional[torch.Tensor] = None, affine: Optional[Sequence[float]] = None,
+                    gain: float = 1.0, bias: float = 0.0) -> torch.Tensor:
     """``resample`` of a volume whose bytes are on the GPU, on the current stream: the linear
     form equals ``resample(vol.astype(float32), target)`` bit for bit, ``nearest=True`` gives
     the binarised label ``resample(vol, target, nearest=True) > 0`` as fp32 {0, 1} (for a
     volume already of the target shape, ``vol > 0``), as ``ProstateDataset.__getitem__`` forms
     them.  Fills ``out`` (a contiguous fp32 (D, H, W) device tensor, e.g. one channel of a
-    batch) or returns a new one.  There is no CPU form: host bytes raise."""
+    batch) or returns a new one.  There is no CPU form: host bytes raise.
+    ``affine`` (twelve doubles, row-major A then t) selects the augmenting entry points:
+    ``resample_affine(vol.astype(float32), target, A, t, gain=gain, bias=bias)`` and, with
+    ``nearest``, ``resample_affine(vol, target, A, t, nearest=True) > 0``, bit for bit."""
     from ._lib import call
     target = tuple(int(v) for v in target)
     if raw.data.device.type != "cuda":
@@ -231,8 +399,19 @@ def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool 
     elif (tuple(out.shape) != target or out.dtype != torch.float32 or not out.is_contiguous()
           or out.device != raw.data.device):
         raise ValueError(f"out must be a contiguous fp32 {target} tensor on {raw.data.device}")
-    call("pcms_resample_label" if nearest else "pcms_resample_linear", raw.data, int(raw.code), *raw.shape,
-         float(raw.slope), float(raw.inter), out, *target)
+    if affine is None:
+        call("pcms_resample_label" if nearest else "pcms_resample_linear", raw.data, int(raw.code), *raw.shape,
+             float(raw.slope), float(raw.inter), out, *target)
+        return out
+    if len(affine) != 12:
+        raise ValueError("affine must hold twelve doubles: row-major A[3][3], then t[3]")
+    host = (ctypes.c_double * 12)(*(float(v) for v in affine))  # read during the call (kernel arguments)
+    if nearest:
+        call("pcms_resample_affine_label", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
+             ctypes.addressof(host), out, *target)
+    else:
+        call("pcms_resample_affine_linear", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
+             ctypes.addressof(host), float(gain), float(bias), out, *target)
     return out
 
 
@@ -253,6 +432,7 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
                            "pcms_amd has no CPU resampling kernel (use the default loader there)")
     images, labels = raw_batch["raw_images"], raw_batch["raw_label"]
     n, m = len(images), len(images[0])
+    aug = raw_batch.get("augment")  # per case: the drawn (affines, label affine, gains, biases), or absent
     with torch.cuda.device(device):
         image = torch.empty((n, m) + target, dtype=torch.float32, device=device)
         label = torch.empty((n, 1) + target, dtype=torch.float32, device=device)
@@ -264,9 +444,13 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
             for c, raw in enumerate(images[i]):
                 if raw is None:
                     image[i, c].zero_()
-                else:
+                elif aug is None:
                     resample_device(up(raw), target, out=image[i, c])
-            resample_device(up(labels[i]), target, nearest=True, out=label[i, 0])
+                else:
+                    resample_device(up(raw), target, out=image[i, c], affine=aug[i]["affine"][c],
+                                    gain=aug[i]["gain"][c], bias=aug[i]["bias"][c])
+            resample_device(up(labels[i]), target, nearest=True, out=label[i, 0],
+                            affine=None if aug is None else aug[i]["label_affine"])
     return {"image": image, "label": label, "case_id": list(raw_batch["case_id"])}
 
 
@@ -284,8 +468,11 @@ class _CollateRaw:
         self.target_size = tuple(int(v) for v in target_size)
 
     def __call__(self, samples: List[Dict]) -> Dict:
-        return {"raw_images": [s["raw_images"] for s in samples], "raw_label": [s["raw_label"] for s in samples],
-                "case_id": [s["case_id"] for s in samples], "target_size": self.target_size}
+        batch = {"raw_images": [s["raw_images"] for s in samples], "raw_label": [s["raw_label"] for s in samples],
+                 "case_id": [s["case_id"] for s in samples], "target_size": self.target_size}
+        if samples and "augment" in samples[0]:  # an augmenting dataset: each case's drawn transform rides along
+            batch["augment"] = [s["augment"] for s in samples]
+        return batch
 
 
 def _find(base: str, case_id: str) -> Optional[str]:
@@ -301,9 +488,16 @@ class ProstateDataset(Dataset):
 
     def __init__(self, data_dir: str, modalities: Optional[List[str]] = None, missing_strategy: str = "zero_fill",
                  target_size: Tuple[int, int, int] = (128, 128, 128), is_training: bool = True,
-                 data_type: str = "BPH", device_resample: bool = False):
+                 data_type: str = "BPH", device_resample: bool = False, augment=None, augment_seed: int = 0):
+        """``augment`` (an ``Augment`` or a dict of its fields; None: off, every sample as
+        before): each case is resampled under a transform drawn by ``draw_transform(augment,
+        augment_seed, epoch, case index)``, one geometry for all its modalities and its label,
+        gain / bias per modality; ``set_epoch`` moves to the next epoch's draws."""
         if missing_strategy not in ("zero_fill", "skip", "duplicate"):
             raise ValueError(f"unsupported missing-modality strategy: {missing_strategy}")
+        self.augment = Augment.of(augment)
+        self.augment_seed = int(augment_seed)
+        self.epoch = 0
         self.data_dir = data_dir
         self.modalities = list(modalities or DEFAULT_MODALITIES)
         self.missing_strategy = missing_strategy
@@ -368,7 +562,44 @@ class ProstateDataset(Dataset):
             return a[0]
         raise ValueError(f"unsupported image dimensions: {a.shape}")
 
+    def set_epoch(self, epoch: int) -> None:
+        """The epoch whose transforms ``__getitem__`` draws (no effect without ``augment``).
+        Call it before iterating the loader: its worker processes start per iteration and
+        take the value along."""
+        self.epoch = int(epoch)
+
+    def _augmented(self, idx: int) -> Dict:
+        """``__getitem__`` under the case's drawn transform: every volume resampled by
+        ``resample_affine`` (also one already of the target shape), or -- ``device_resample`` --
+        handed over undecoded with the twelve doubles and the gain / bias it is to be resampled
+        with."""
+        case = self.case_list[idx]
+        files = case["modality_files"]
+        tf = draw_transform(self.augment, self.augment_seed, self.epoch, idx, len(self.modalities))
+        if self.device_resample:
+            raws = [read_nifti_raw(files[m]) if m in files else None for m in self.modalities]
+            lab = read_nifti_raw(case["label_path"])
+            aug = {"affine": [None if r is None else tf.affine12(r.shape, self.target_size) for r in raws],
+                   "label_affine": tf.affine12(lab.shape, self.target_size), "gain": tf.gain, "bias": tf.bias}
+            return {"raw_images": raws, "raw_label": lab, "case_id": case["case_id"], "augment": aug}
+        chans = []
+        for c, m in enumerate(self.modalities):
+            p = files.get(m)
+            if p is None:  # zero_fill stays zero: no bias on a channel that is not there
+                chans.append(np.zeros(self.target_size, dtype=np.float32))
+                continue
+            vol = self._first_volume(read_nifti(p)).astype(np.float32)
+            A, t = tf.affine(vol.shape, self.target_size)
+            chans.append(resample_affine(vol, self.target_size, A, t, gain=tf.gain[c], bias=tf.bias[c]))
+        lab = self._first_volume(read_nifti(case["label_path"]))
+        A, t = tf.affine(lab.shape, self.target_size)
+        label = (resample_affine(lab, self.target_size, A, t, nearest=True) > 0).astype(np.float32)[None]
+        return {"image": torch.from_numpy(np.stack(chans, 0)).float(), "label": torch.from_numpy(label),
+                "case_id": case["case_id"]}
+
     def __getitem__(self, idx: int) -> Dict:
+        if self.augment is not None:
+            return self._augmented(idx)
         case = self.case_list[idx]
         if self.device_resample:
             # undecoded volumes for assemble_batch (None: a zero_fill channel); no numpy resampling
@@ -396,15 +627,19 @@ class ProstateDataset(Dataset):
 def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, modalities=None,
                    missing_strategy: str = "zero_fill", target_size=(128, 128, 128), num_workers: int = 0,
                    is_training: bool = True, data_type: str = "BPH", indices=None, rank: int = 0,
-                   world_size: int = 1, device_resample: bool = False) -> DataLoader:
+                   world_size: int = 1, device_resample: bool = False, augment=None,
+                   augment_seed: int = 0) -> DataLoader:
     """script/data_loader.py:421-466 (pinned host batches; Trainer stages them to the GPU on
     a copy stream one batch ahead).  ``world_size > 1``: each rank iterates its own
     DistributedSampler shard (call ``loader.sampler.set_epoch(epoch)`` every epoch).
     ``device_resample``: the batches carry the files' undecoded volumes (``RawVolume`` lists,
-    same cases in the same order); ``assemble_batch`` resamples them on the GPU."""
+    same cases in the same order); ``assemble_batch`` resamples them on the GPU.
+    ``augment`` / ``augment_seed``: training-time augmentation (``ProstateDataset``); call the
+    dataset's ``set_epoch(epoch)`` every epoch (through a ``Subset``: ``loader.dataset.dataset``),
+    ``Trainer.train`` does.  Both kinds of loader give equal batches with it too."""
     ds = ProstateDataset(data_dir, modalities=modalities, missing_strategy=missing_strategy,
                          target_size=target_size, is_training=is_training, data_type=data_type,
-                         device_resample=device_resample)
+                         device_resample=device_resample, augment=augment, augment_seed=augment_seed)
     collate = _CollateRaw(target_size) if device_resample else None
     if indices is not None:
         ds = torch.utils.data.Subset(ds, indices)

@@ -22,7 +22,10 @@ Config keys follow utils/trainer.py:40-49 (``device``, ``learning_rate``, ``batc
 ``num_epochs``, ``save_dir``, ``validation`` ...) plus ``loss`` ('dice' | 'bce_dice'),
 ``precision`` ('bf16' | 'fp32'), ``checkpoint_decoder``, ``device_resample`` (the ``data_dir``
 loaders hand over the files' undecoded volumes and ``data.assemble_batch`` resamples them on
-the GPU, on the copy stream beside the previous step; same batches bit for bit), and the step
+the GPU, on the copy stream beside the previous step; same batches bit for bit), ``augment`` /
+``augment_seed`` (training-time augmentation of the ``data_dir`` training loader, see
+``data.Augment``: random flips, rotations, zoom, shifts and per-modality gain / bias, drawn per
+case and epoch; validation never augments; both loaders give the same batches), and the step
 variants of the other reference trainers:
   ``max_grad_norm``  clip_grad_norm_(max_norm) before Adam (train_bph.py:166,
                      train_bph_cv.py:311 use 1.0): one fused norm pass, the clip coefficient
@@ -111,7 +114,10 @@ class BaseTrainer:
                               target_size=tuple(self.config.get("target_size", (128, 128, 128))),
                               is_training=mode == "train", data_type=self.config.get("data_type", "BPH"),
                               rank=self.rank, world_size=self.world_size,
-                              device_resample=bool(self.config.get("device_resample", False)))
+                              device_resample=bool(self.config.get("device_resample", False)),
+                              # the training loader only: validation never augments
+                              augment=self.config.get("augment") if mode == "train" else None,
+                              augment_seed=int(self.config.get("augment_seed", 0)))
 
     def _broadcast_params(self):
         eng = self.model.engine()
@@ -316,6 +322,11 @@ class BaseTrainer:
                 sampler = getattr(ld, "sampler", None)
                 if hasattr(sampler, "set_epoch"):
                     sampler.set_epoch(epoch)
+            ds = getattr(self.train_loader, "dataset", None)
+            while isinstance(ds, torch.utils.data.Subset):
+                ds = ds.dataset
+            if hasattr(ds, "set_epoch"):  # an augmenting dataset draws this epoch's transforms
+                ds.set_epoch(epoch)
             train_loss = self._mean_over_ranks(self.train_epoch())
             if self.distributed:  # validate with rank 0's running statistics everywhere
                 dist.broadcast(self.model.engine().flat_bn, src=0)
