@@ -450,6 +450,37 @@ int pcms_resample_affine_label(const void* src, int datatype, int Di, int Hi, in
                                double scl_inter, const double* affine12, float* out, int D, int H, int W,
                                hipStream_t s);
 
+/* ---- case prediction: predict.py's host forms on the device (script/predict.py) ------ */
+/* lohi[0] / lohi[1]: the minimum / maximum of the n decoded fp32 values of a volume (decoded
+ * as pcms_resample_linear decodes a voxel, so a negative scl_slope is seen), what
+ * predict.normalise takes from numpy's min / max: a NaN anywhere gives NaN for both.  src
+ * needs its element's alignment only.  Two launches, deterministic: per-workgroup partials in
+ * work (pcms_volume_minmax_work_floats(n) floats, device memory), then one workgroup folds them.
+ * An unknown datatype, n < 1, a NULL or misaligned pointer: negative, no launch.            */
+int pcms_volume_minmax_work_floats(long n);
+int pcms_volume_minmax(const void* src, int datatype, long n, double scl_slope, double scl_inter, float* lohi,
+                       float* work, hipStream_t s);
+/* pcms_resample_linear with every source voxel v replaced by predict.normalise's value: with
+ * lo = lohi[0], hi = lohi[1] (DEVICE floats, e.g. pcms_volume_minmax's) and den =
+ * fl32((double)hi - (double)lo), the corner is fl32(fl32(v - lo) / den), or 0 when den == 0.
+ * Equal to data.resample(predict.normalise(vol), (D, H, W)) bit for bit; with all three axes
+ * identical a plain normalise.  Rejects what pcms_resample_linear rejects and a NULL lohi.    */
+int pcms_resample_linear_norm(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
+                              double scl_inter, const float* lohi, float* out, int D, int H, int W, hipStream_t s);
+/* predict.tta_mean: probs holds k contiguous D x H x W fp32 volumes, volume j computed from the
+ * input flipped along the axes in flipmask[j] (bit 0: D, bit 1: H, bit 2: W; k HOST ints copied
+ * into the kernel arguments).  out = (((p0 + flip(p1)) + flip(p2)) + ...) / (float)k, every fp32
+ * sum and the quotient rounded on its own; out must not overlap probs.  1 <= k <= 8 (the
+ * distinct flip sets), flipmask[0] == 0, every flipmask[j] in 0..7, else negative, no launch. */
+int pcms_flip_mean(const float* probs, int k, const int* flipmask, float* out, int D, int H, int W, hipStream_t s);
+/* predict.mask_on_grid in one launch: pcms_resample_linear's gather on an fp32 Dt x Ht x Wt
+ * volume, onto the D x H x W grid; mask[i] = value > threshold ? 1 : 0 (strict; bytes), and the
+ * fp32 value itself to prob_native unless that is NULL.  Zero (so background) where an axis is
+ * sampled at or past n_in - 0.5.  A dimension < 1, a NULL prob or mask, a misaligned float
+ * pointer: negative, no launch.                                                            */
+int pcms_prob_to_mask(const float* prob, int Dt, int Ht, int Wt, float threshold, unsigned char* mask,
+                      float* prob_native, int D, int H, int W, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

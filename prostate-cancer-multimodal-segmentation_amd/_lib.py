@@ -119,6 +119,11 @@ SIGNATURES = {
     "pcms_resample_label": "piiiiddpiiis",
     "pcms_resample_affine_linear": "piiiiddpffpiiis",  # affine12: a host pointer (ctypes.addressof)
     "pcms_resample_affine_label": "piiiiddppiiis",
+    "pcms_volume_minmax_work_floats": "l",
+    "pcms_volume_minmax": "pilddpps",
+    "pcms_resample_linear_norm": "piiiiddppiiis",
+    "pcms_flip_mean": "pippiiis",  # flipmask: a host pointer (ctypes.addressof)
+    "pcms_prob_to_mask": "piiifppiiis",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

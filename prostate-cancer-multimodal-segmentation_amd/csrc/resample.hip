@@ -10,9 +10,8 @@
 // (D, then H, then W); an 8-corner gather lerped in that order gives every intermediate the
 // same two operands and so the same roundings.  Every product and sum below must round on its
 // own, as numpy's do: no contraction into FMAs anywhere in this file.
-#include <cmath>
+#include "resample_common.h"
 
-#include "common.h"
 #include "pcms_hip.h"
 
 #pragma clang fp contract(off)
@@ -21,87 +20,19 @@ namespace {
 
 constexpr int TPB = 256;
 
-// One axis of the output grid, formed on the host: ratio = (double)n_in / (double)n_out (numpy's
-// n_in / n_out), edge = n_in - 0.5 (zero from there on), ident: n_in == n_out (the pass is skipped)
-struct Axis {
-  double ratio, edge;
-  int n_in, n_out, ident;
-};
-struct Scale {
-  double slope, inter;
-  int on;  // read_nifti: slope not in (0, 1) or inter != 0, with slope 0 meaning 1
-};
-
-inline Axis make_axis(int n_in, int n_out) {
-  return Axis{(double)n_in / (double)n_out, (double)n_in - 0.5, n_in, n_out, n_in == n_out ? 1 : 0};
-}
-inline Scale make_scale(double slope, double inter) {
-  const int on = (!(slope == 0.0 || slope == 1.0) || inter != 0.0) ? 1 : 0;
-  return Scale{slope == 0.0 ? 1.0 : slope, inter, on};
-}
-
-// a voxel as read_nifti hands it on: fp64 raw * slope + inter when scaling applies (product
-// and sum rounded separately), else the raw value itself
-template <typename T> __device__ __forceinline__ double scaled(T raw, const Scale& sc) {
-  return (double)raw * sc.slope + sc.inter;
-}
-// the image sample ProstateDataset.__getitem__ resamples: that value as fp32
-template <typename T> __device__ __forceinline__ float image_value(T raw, const Scale& sc) {
-  return sc.on ? (float)scaled(raw, sc) : (float)raw;
-}
-
-struct Tap {
-  long lo, hi;  // clamped neighbours
-  double w;
-  bool outside;
-};
-__device__ __forceinline__ Tap linear_tap(const Axis& a, int i) {
-  Tap t;
-  if (a.ident) {
-    t.lo = t.hi = i;
-    t.w = 0.0;
-    t.outside = false;
-    return t;
-  }
-  const double c = (double)i * a.ratio;
-  const double f = floor(c);
-  const long i0 = (int)f;  // c < n_in <= INT_MAX
-  t.w = c - f;
-  t.lo = i0 < a.n_in - 1 ? i0 : a.n_in - 1;  // c >= 0: no lower clamp can bind
-  t.hi = i0 + 1 < a.n_in - 1 ? i0 + 1 : a.n_in - 1;
-  t.outside = !(c < a.edge);
-  return t;
-}
-__device__ __forceinline__ double lerp(double a, double b, double w) { return a * (1.0 - w) + b * w; }
-
 template <typename T>
 __global__ void __launch_bounds__(TPB) resample_linear_kernel(const T* __restrict__ src, float* __restrict__ out,
                                                               Axis ad, Axis ah, Axis aw, Scale sc) {
   const long HW = (long)ah.n_out * aw.n_out;
   const long total = (long)ad.n_out * HW;
-  const long sH = aw.n_in, sD = (long)ah.n_in * aw.n_in;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int d = (int)(i / HW);
     const long r = i - d * HW;
     const int h = (int)(r / aw.n_out), w = (int)(r - (long)h * aw.n_out);
     const Tap td = linear_tap(ad, d), th = linear_tap(ah, h), tw = linear_tap(aw, w);
     float res = 0.f;
-    if (!(td.outside || th.outside || tw.outside)) {
-      double vh[2];
-#pragma unroll
-      for (int jw = 0; jw < 2; ++jw) {
-        const long xw = jw ? tw.hi : tw.lo;
-        double vd[2];
-#pragma unroll
-        for (int jh = 0; jh < 2; ++jh) {
-          const long xh = (jh ? th.hi : th.lo) * sH + xw;
-          const double a = (double)image_value(src[td.lo * sD + xh], sc);
-          vd[jh] = ad.ident ? a : lerp(a, (double)image_value(src[td.hi * sD + xh], sc), td.w);
-        }
-        vh[jw] = ah.ident ? vd[0] : lerp(vd[0], vd[1], th.w);
-      }
-      res = (float)(aw.ident ? vh[0] : lerp(vh[0], vh[1], tw.w));
-    }
+    if (!(td.outside || th.outside || tw.outside))
+      res = gather_linear(ad, ah, aw, td, th, tw, [&](long x) { return (double)image_value(src[x], sc); });
     out[i] = res;
   }
 }
@@ -164,19 +95,7 @@ int resample(bool label, const void* src, int code, int Di, int Hi, int Wi, doub
   if (((uintptr_t)out) % alignof(float) != 0) return -1;
   const Axis ad = make_axis(Di, D), ah = make_axis(Hi, H), aw = make_axis(Wi, W);
   const Scale sc = make_scale(slope, inter);
-  switch (code) {  // NIfTI-1 datatype codes (data._NIFTI_DTYPES)
-    case 2: return launch<uint8_t>(label, src, out, ad, ah, aw, sc, s);
-    case 4: return launch<int16_t>(label, src, out, ad, ah, aw, sc, s);
-    case 8: return launch<int32_t>(label, src, out, ad, ah, aw, sc, s);
-    case 16: return launch<float>(label, src, out, ad, ah, aw, sc, s);
-    case 64: return launch<double>(label, src, out, ad, ah, aw, sc, s);
-    case 256: return launch<int8_t>(label, src, out, ad, ah, aw, sc, s);
-    case 512: return launch<uint16_t>(label, src, out, ad, ah, aw, sc, s);
-    case 768: return launch<uint32_t>(label, src, out, ad, ah, aw, sc, s);
-    case 1024: return launch<int64_t>(label, src, out, ad, ah, aw, sc, s);
-    case 1280: return launch<uint64_t>(label, src, out, ad, ah, aw, sc, s);
-    default: return -1;
-  }
+  return for_datatype(code, [&](auto t) { return launch<decltype(t)>(label, src, out, ad, ah, aw, sc, s); });
 }
 
 // ---- training-time augmentation: the same gather under a full 3x4 affine (data.resample_affine) ----
@@ -313,19 +232,8 @@ int resample_affine(bool label, const void* src, int code, int Di, int Hi, int W
   const Affine m{Row{a[0], a[1], a[2], a[9]}, Row{a[3], a[4], a[5], a[10]}, Row{a[6], a[7], a[8], a[11]}};
   const Dims g{Di, Hi, Wi, D, H, W};
   const Scale sc = make_scale(slope, inter);
-  switch (code) {
-    case 2: return launch_affine<uint8_t>(label, src, out, m, g, sc, gain, bias, s);
-    case 4: return launch_affine<int16_t>(label, src, out, m, g, sc, gain, bias, s);
-    case 8: return launch_affine<int32_t>(label, src, out, m, g, sc, gain, bias, s);
-    case 16: return launch_affine<float>(label, src, out, m, g, sc, gain, bias, s);
-    case 64: return launch_affine<double>(label, src, out, m, g, sc, gain, bias, s);
-    case 256: return launch_affine<int8_t>(label, src, out, m, g, sc, gain, bias, s);
-    case 512: return launch_affine<uint16_t>(label, src, out, m, g, sc, gain, bias, s);
-    case 768: return launch_affine<uint32_t>(label, src, out, m, g, sc, gain, bias, s);
-    case 1024: return launch_affine<int64_t>(label, src, out, m, g, sc, gain, bias, s);
-    case 1280: return launch_affine<uint64_t>(label, src, out, m, g, sc, gain, bias, s);
-    default: return -1;
-  }
+  return for_datatype(
+      code, [&](auto t) { return launch_affine<decltype(t)>(label, src, out, m, g, sc, gain, bias, s); });
 }
 
 }  // namespace

@@ -150,8 +150,35 @@ def read_nifti_raw(path: str) -> RawVolume:
     return RawVolume(data, int(h["datatype"]), shape, h["scl_slope"], h["scl_inter"])
 
 
-def write_nifti(path: str, arr_zyx: np.ndarray, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> None:
-    """Minimal NIfTI-1 writer (single file, little endian) for tests and synthetic data."""
+# the header fields that place a volume in space: (name, byte offset, struct format)
+_GEOMETRY_FIELDS = (("pixdim", 76, "4f"), ("xyzt_units", 123, "B"), ("qform_code", 252, "h"), ("sform_code", 254, "h"),
+                    ("quatern_b", 256, "f"), ("quatern_c", 260, "f"), ("quatern_d", 264, "f"),
+                    ("qoffset_x", 268, "f"), ("qoffset_y", 272, "f"), ("qoffset_z", 276, "f"),
+                    ("srow_x", 280, "4f"), ("srow_y", 296, "4f"), ("srow_z", 312, "4f"))
+
+
+def read_nifti_geometry(path: str) -> dict:
+    """Where the file's voxel grid lies in space (either byte order): ``pixdim`` (pixdim[0..3],
+    qfac first), ``xyzt_units``, ``qform_code`` / ``sform_code``, ``quatern_b/c/d``,
+    ``qoffset_x/y/z`` and ``srow_x/y/z`` (four floats each) -- what SimpleITK's
+    ``CopyInformation`` carries over as spacing, origin and direction, and what
+    ``write_nifti(..., geometry=...)`` writes back."""
+    endian = read_nifti_header(path)["endian"]
+    with _open(path) as f:
+        raw = f.read(348)
+    geo = {}
+    for name, off, fmt in _GEOMETRY_FIELDS:
+        v = struct.unpack_from(endian + fmt, raw, off)
+        geo[name] = v[0] if len(v) == 1 else tuple(v)
+    return geo
+
+
+def write_nifti(path: str, arr_zyx: np.ndarray, spacing: Sequence[float] = (1.0, 1.0, 1.0),
+                geometry: Optional[dict] = None) -> None:
+    """Minimal NIfTI-1 writer (single file, little endian) for tests, synthetic data and
+    predicted masks.  ``geometry`` (a ``read_nifti_geometry`` dict): its fields are written too
+    and ``spacing`` is taken from its pixdim[1..3]; without it the header carries the spacing
+    alone."""
     codes = {np.dtype(v): k for k, v in _NIFTI_DTYPES.items()}
     a = np.ascontiguousarray(arr_zyx)
     if a.dtype not in codes:
@@ -163,9 +190,13 @@ def write_nifti(path: str, arr_zyx: np.ndarray, spacing: Sequence[float] = (1.0,
     dims = [len(shape_xyz)] + list(shape_xyz) + [1] * (7 - len(shape_xyz))
     struct.pack_into("<8h", hdr, 40, *dims)
     struct.pack_into("<hh", hdr, 70, codes[a.dtype], a.dtype.itemsize * 8)
-    pix = [1.0] + list(spacing) + [1.0] * (7 - len(spacing))
+    pix =[1.0] + list(spacing) + [1.0] * (7 - len(spacing))
     struct.pack_into("<8f", hdr, 76, *pix[:8])
     struct.pack_into("<fff", hdr, 108, 352.0, 1.0, 0.0)
+    if geometry is not None:  # pixdim[0..3] among them: the geometry's spacing replaces `spacing`
+        for name, off, fmt in _GEOMETRY_FIELDS:
+            v = geometry[name]
+            struct.pack_into("<" + fmt, hdr, off, *(v if isinstance(v, (tuple, list)) else (v,)))
     hdr[344:348] = b"n+1\x00"
     data = bytes(hdr) + a.tobytes()
     with (gzip.open(path, "wb") if path.endswith(".gz") else open(path, "wb")) as f:

@@ -12,15 +12,24 @@
   with the reference image's voxel spacing when one is given (:172-196).  ``saliency`` ->
   (5, D, H, W) input gradient of the summed probabilities (no reference equivalent in
   predict.py; plain autograd through the reference model gives the same quantity).
+
+Case prediction on the training grid: ``predict_case(case_dir)`` takes a case from
+its raw NIfTI files to a uint8 mask on the native grid of its reference image, every per-voxel
+step in a HIP kernel; ``save_case`` writes it with that image's full geometry.  The host forms
+``normalise`` / ``prepare_case`` / ``tta_mean`` / ``mask_on_grid`` define what the kernels
+compute, bit for bit.
 """
 from __future__ import annotations
 
+import ctypes
+import dataclasses
 import os
-from typing import List, Optional, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
+from . import data as _data
 from .data import read_nifti, read_nifti_header, write_nifti
 from .models.unet3d import UNet3D, load_weights
 
@@ -51,6 +60,166 @@ def load_multimodal_images(case_dir: str, handle_missing: str = "zero_fill") -> 
         img = (img - lo) / (hi - lo) if hi - lo != 0 else np.zeros_like(img, dtype=np.float32)
         images.append(img.astype(np.float32))
     return np.stack(images, axis=0), list(MODALITIES)
+
+
+def normalise(vol: np.ndarray) -> np.ndarray:
+    """Min-max normalisation of one volume to [0, 1] as ``load_multimodal_images`` forms a
+    channel, bit for bit: ``v = vol.astype(float32)``, ``lo = v.min()``, ``hi = v.max()``,
+    ``den = float32(float64(hi) - float64(lo))``, the result ``(v - lo) / den`` in fp32, or
+    zeros when ``den == 0``.  A NaN in the volume makes ``lo``, ``hi`` and every voxel NaN."""
+    v = np.asarray(vol).astype(np.float32)
+    lo, hi = v.min(), v.max()
+    with np.errstate(over="ignore", invalid="ignore"):
+        den = np.float32(np.float64(hi) - np.float64(lo))
+        if den == 0:
+            return np.zeros_like(v)
+        return (v - lo) / den
+
+
+_normalise = normalise  # prepare_case's keyword of the same name shadows the function there
+
+
+def _case_files(case_dir: str) -> List[Optional[str]]:
+    """Per modality the first ``.nii`` of its folder in sorted order, or None."""
+    paths = []
+    for modality in MODALITIES:
+        mdir = os.path.join(case_dir, modality)
+        if not os.path.exists(mdir):
+            raise FileNotFoundError(f"modality directory missing: {mdir}")
+        files = sorted(f for f in os.listdir(mdir) if f.endswith(".nii"))
+        paths.append(os.path.join(mdir, files[0]) if files else None)
+    return paths
+
+
+def _case_plan(case_dir: str, target_size, handle_missing: str):
+    """(paths, the grid every channel is formed on, the channel a missing modality copies or
+    None for zeros): what ``prepare_case`` and ``prepare_case_device`` decide alike."""
+    if handle_missing not in ("zero_fill", "skip", "duplicate"):
+        raise ValueError(f"unsupported missing-modality strategy: {handle_missing}")
+    paths = _case_files(case_dir)
+    present = [c for c, p in enumerate(paths) if p is not None]
+    if not present or (handle_missing == "skip" and len(present) < len(paths)):
+        missing = [m for m, p in zip(MODALITIES, paths) if p is None]
+        raise FileNotFoundError(f"no .nii file for {missing} in {case_dir}")
+    if target_size is not None:
+        grid = tuple(int(v) for v in target_size)
+    else:
+        shapes = {p: tuple(read_nifti_header(p)["shape_xyz"][:3][::-1]) for p in paths if p is not None}
+        if len(set(shapes.values())) != 1:
+            raise ValueError(f"target_size=None needs modalities of one shape, got {sorted(set(shapes.values()))}")
+        grid = shapes[paths[present[0]]]
+    return paths, grid, present[0] if handle_missing == "duplicate" else None
+
+
+def _first_volume(a: np.ndarray) -> np.ndarray:
+    if a.ndim not in (3, 4):
+        raise ValueError(f"unsupported image dimensions: {a.shape}")
+    return a if a.ndim == 3 else a[0]
+
+
+def prepare_case(case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
+                 handle_missing: str = "zero_fill", normalise: bool = True) -> np.ndarray:
+    """The five modalities of a case on one grid, (5, D, H, W) float32: per modality the first
+    ``.nii`` in sorted order (volume 0 of a 4-D file), ``normalise``d when asked, else as fp32,
+    then ``data.resample(., target_size)`` (linear).  A missing modality is zeros
+    ('zero_fill'), the first present modality's channel ('duplicate') or an error ('skip').
+    ``target_size=None``: no resampling; the present shapes must agree (ValueError).
+    With ``normalise=False`` a channel is the one the default training loader forms for the
+    file; with ``normalise=True`` it is ``load_multimodal_images``' channel on the grid."""
+    paths, grid, dup = _case_plan(case_dir, target_size, handle_missing)
+    chans: List[Optional[np.ndarray]] = []
+    for p in paths:
+        if p is None:
+            chans.append(None)
+            continue
+        vol = _first_volume(read_nifti(p))
+        vol = _normalise(vol) if normalise else vol.astype(np.float32)
+        chans.append(_data.resample(vol, grid))
+    fill = np.zeros(grid, dtype=np.float32) if dup is None else chans[dup]
+    return np.stack([fill if c is None else c for c in chans], axis=0)
+
+
+def tta_mean(probs: Sequence[np.ndarray], flips: Sequence[Tuple[int, ...]]) -> np.ndarray:
+    """Test-time-augmentation mean, (D, H, W) float32: ``probs[j]`` is the probability volume
+    of the input flipped along the axes ``flips[j]`` (out of 0, 1, 2; ``flips[0]`` must be
+    ``()``), flipped back and summed in order in fp32, divided by ``float32(k)``."""
+    flips = [tuple(int(a) for a in f) for f in flips]
+    if len(probs) != len(flips) or not flips or flips[0] != ():
+        raise ValueError("tta_mean needs one flip set per volume, the first of them ()")
+    acc = np.asarray(probs[0], dtype=np.float32)
+    for p, f in zip(probs[1:], flips[1:]):
+        acc = acc + np.flip(np.asarray(p, dtype=np.float32), f)
+    return acc / np.float32(len(flips))
+
+
+def mask_on_grid(prob: np.ndarray, native_shape: Sequence[int], threshold: float = 0.5):
+    """A probability volume on the training grid -> ``(uint8 mask, float32 probabilities)`` on
+    the ``native_shape`` grid: ``data.resample(prob.astype(float32), native_shape)`` and its
+    strict ``> float32(threshold)``.  This is the exact inverse geometry of the forward map:
+    native index i samples target coordinate ``i * n_tgt / n_nat``.  ``data.resample``'s edge
+    rule holds here too: a sample at or past ``n_tgt - 0.5`` is 0, so where the native grid is
+    finer than the training grid the trailing fraction of a training voxel reads as
+    background."""
+    prob_native = _data.resample(np.asarray(prob).astype(np.float32), tuple(int(v) for v in native_shape))
+    return (prob_native > np.float32(threshold)).astype(np.uint8), prob_native
+
+
+def _flip_masks(flips) -> List[int]:
+    """Flip sets (tuples of axes out of 0, 1, 2) as pcms_flip_mean's bit masks, () first."""
+    masks = [0]
+    for f in flips:
+        f = tuple(int(a) for a in f)
+        if not f or any(a not in (0, 1, 2) for a in f) or len(set(f)) != len(f):
+            raise ValueError(f"a flip set holds distinct axes out of (0, 1, 2), got {f!r}")
+        masks.append(sum(1 << a for a in f))
+    return masks
+
+
+def prepare_case_device(case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
+                        handle_missing: str = "zero_fill", normalise: bool = True,
+                        device="cuda") -> torch.Tensor:
+    """``prepare_case`` on the GPU, bit for bit, as the (1, 5, D, H, W) fp32 network input: each
+    file's undecoded bytes (``data.read_nifti_raw``) go up once; pcms_volume_minmax and
+    pcms_resample_linear_norm form the normalised channel, ``data.resample_device`` the plain
+    one.  Everything is enqueued on the current stream."""
+    from ._lib import call, query
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"prepare_case_device needs a GPU, not '{device}': pcms_amd has no CPU fallback -- "
+                           "use predict.prepare_case on the host")
+    paths, grid, dup = _case_plan(case_dir, target_size, handle_missing)
+    with torch.cuda.device(device):
+        x = torch.empty((1, len(paths)) + grid, dtype=torch.float32, device=device)
+        lohi = torch.empty(2, dtype=torch.float32, device=device)
+        for c, p in enumerate(paths):
+            if p is None:
+                continue
+            raw = _data.read_nifti_raw(p).to(device)
+            if not normalise:
+                _data.resample_device(raw, grid, out=x[0, c])
+                continue
+            n = int(np.prod(raw.shape))
+            work = torch.empty(query("pcms_volume_minmax_work_floats", n), dtype=torch.float32, device=device)
+            call("pcms_volume_minmax", raw.data, int(raw.code), n, float(raw.slope), float(raw.inter), lohi, work)
+            call("pcms_resample_linear_norm", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
+                 lohi, x[0, c], *grid)
+        for c, p in enumerate(paths):
+            if p is None and dup is None:
+                x[0, c].zero_()
+            elif p is None:
+                x[0, c].copy_(x[0, dup])
+    return x
+
+
+@dataclasses.dataclass
+class CasePrediction:
+    """``ModelPredictor.predict_case``'s result: the uint8 ``mask`` and, when asked for, the fp32
+    ``probability`` on the native (z, y, x) grid of ``reference_path``, whose
+    ``data.read_nifti_geometry`` is ``geometry``."""
+    mask: np.ndarray
+    probability: Optional[np.ndarray]
+    reference_path: str
+    geometry: dict
 
 
 def preprocess_image(image: np.ndarray) -> torch.Tensor:
@@ -85,3 +254,48 @@ class ModelPredictor:
         if reference_image_path and os.path.exists(reference_image_path):
             spacing = read_nifti_header(reference_image_path)["spacing"][:3]
         write_nifti(output_path, (prediction > 0.5).astype(np.uint8), spacing=spacing)
+
+    def predict_case(self, case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
+                     handle_missing: str = "zero_fill", normalise: bool = True, threshold: float = 0.5,
+                     tta_flips: Sequence[Tuple[int, ...]] = (), output_like: Optional[str] = None,
+                     return_probability: bool = False) -> CasePrediction:
+        """One case from its raw NIfTI files to a mask on its native grid, on the GPU:
+        ``prepare_case_device`` -> the network on the input and on its copies flipped along each
+        of ``tta_flips`` (tuples of axes out of 0, 1, 2) in one batch -> pcms_flip_mean
+        (``tta_mean``; skipped without flips) -> pcms_prob_to_mask (``mask_on_grid``) -> one copy
+        of the mask to the host (and of the probabilities with ``return_probability``).  The
+        native grid is that of ``output_like`` (any NIfTI file, e.g. the label) or else of the
+        first present modality's file.  ``normalise=False`` feeds the network what the training
+        loader feeds it; ``normalise=True`` what ``load_multimodal_images`` would, resampled."""
+        from ._lib import call
+        masks = _flip_masks(tta_flips)
+        x = prepare_case_device(case_dir, target_size, handle_missing, normalise, self.device)  # raises if none present
+        reference = output_like if output_like is not None else \
+            next(p for p in _case_files(case_dir) if p is not None)
+        native = tuple(int(v) for v in read_nifti_header(reference)["shape_xyz"][:3][::-1])
+        geometry = _data.read_nifti_geometry(reference)
+        grid = tuple(x.shape[2:])
+        with torch.no_grad(), torch.cuda.device(self.device):
+            batch = torch.cat([x] + [torch.flip(x, dims=[2 + a for a in f]) for f in tta_flips], dim=0)
+            probs = self.model.predict(batch).float().contiguous()  # (k, 1, D, H, W)
+            if len(masks) > 1:
+                host = (ctypes.c_int * len(masks))(*masks)  # read during the call (kernel arguments)
+                prob = torch.empty(grid, dtype=torch.float32, device=self.device)
+                call("pcms_flip_mean", probs, len(masks), ctypes.addressof(host), prob, *grid)
+            else:
+                prob = probs[0, 0]
+            mask = torch.empty(native, dtype=torch.uint8, device=self.device)
+            prob_native = torch.empty(native, dtype=torch.float32, device=self.device) if return_probability else None
+            call("pcms_prob_to_mask", prob, *grid, float(threshold), mask, prob_native, *native)
+        return CasePrediction(mask.cpu().numpy(), prob_native.cpu().numpy() if return_probability else None,
+                              reference, geometry)
+
+    def save_case(self, result: CasePrediction, output_path: str) -> None:
+        """Write ``result.mask`` as a NIfTI file with the reference image's spacing, qform and
+        sform (the reference's ``CopyInformation``); ValueError if the mask is not on that
+        image's grid."""
+        shape = tuple(int(v) for v in read_nifti_header(result.reference_path)["shape_xyz"][:3][::-1])
+        if tuple(result.mask.shape) != shape:
+            raise ValueError(f"mask of shape {tuple(result.mask.shape)} is not on the grid {shape} of "
+                             f"{result.reference_path}")
+        write_nifti(output_path, result.mask.astype(np.uint8), geometry=result.geometry)
