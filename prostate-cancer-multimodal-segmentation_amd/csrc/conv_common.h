@@ -1,4 +1,4 @@
-// Device helpers shared by the 3x3x3 convolution kernels (conv3.hip, stem.hip), gfx950.
+// Device helpers shared by the 3x3x3 convolution kernels (conv3_*.hip, stem.hip), gfx950.
 #pragma once
 #include "common.h"
 #include <algorithm>

@@ -2,8 +2,14 @@
 // off, to see which part bounds the chunk loop.  F bits: 1 halo DMA reads nothing (the
 // instructions still issue), 2 B loads all hit one L1 line, 4 no output stores, 8 no A
 // fragment reads after the first tap, 16 no MFMAs.
-#include "../../prostate-cancer-multimodal-segmentation_amd/csrc/conv3.hip"
+#include "../../prostate-cancer-multimodal-segmentation_amd/csrc/conv3_big.hip"
 namespace {
+// this experiment still loads B as two 16-B fragments per tap (the product kernel's pack made it
+// one: its vm_wait1); the wait on both
+template <int N> __device__ __forceinline__ void vm_wait2(s16x8_t& a, s16x8_t& b) {
+  static_assert(N >= 0 && N <= 63, "vmcnt");
+  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
+}
 template <int F>
 __global__ void __launch_bounds__(kBgThreads, 1) big_exp_kernel(Conv3Params p, uint32_t x0bytes,
                                                                      uint32_t x1bytes) {

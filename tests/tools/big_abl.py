@@ -1,5 +1,5 @@
 """Big-box conv ablation on the box (test tooling): the product kernel and BG_ABL builds
-(tests/tools/ab_build.sh <suf> -DBG_ABL=<bits>, see conv3.hip) timed back to back on the
+(tests/tools/ab_build.sh <suf> -DBG_ABL=<bits>, see conv3_bigbox.h) timed back to back on the
 level-0 / level-1 shapes, with the shader clock over the launches (bench.ClockProbe).
 Usage: python tests/tools/big_abl.py [lib suffix ...]   ("" = the product library)."""
 import json

@@ -1,5 +1,5 @@
 """Weight-gradient ablation on the box (test tooling): the product kernel and WGRAD_ABL builds
-(tests/tools/ab_build.sh <suf> -DWGRAD_ABL=<bits>, see conv3.hip) timed back to back on the
+(tests/tools/ab_build.sh <suf> -DWGRAD_ABL=<bits>, see conv3_wgrad.hip) timed back to back on the
 level-0..2 shapes of config 2, with the shader clock over the launches (bench.ClockProbe).
 WGRAD_ABL_SHAPES=deep: the level-3/4 shapes instead.
 Usage: python tests/tools/wgrad_abl.py [lib suffix ...]   ("" = the product library, "k32" = the
