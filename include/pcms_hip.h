@@ -481,6 +481,29 @@ int pcms_flip_mean(const float* probs, int k, const int* flipmask, float* out, i
 int pcms_prob_to_mask(const float* prob, int Dt, int Ht, int Wt, float threshold, unsigned char* mask,
                       float* prob_native, int D, int H, int W, hipStream_t s);
 
+/* ---- mask post-processing: predict.py's label_components / postprocess on the device ---- */
+/* Foreground is mask != 0 (mask == 0 with invert = 1), the flat index of a voxel is
+ * (d H + h) W + w, connectivity is 6, 18 or 26 (offsets in {-1, 0, 1}, at most 1 / 2 / 3 of
+ * them nonzero).  work: pcms_components_work_ints(D, H, W) int32 of device memory (negative for
+ * a dimension < 1 or a volume too large for an int-sized workspace: more than 2^30 - 32 voxels).
+ * Both entry points zero work[0] first and a kernel that runs into one of its iteration caps
+ * stores a nonzero status there (it cannot, the caps are the proven bounds), so
+ * work[0] must read 0 after the stream has run.  Everything is enqueued on s: no allocation,
+ * no host synchronisation, no device-to-host read.  NULL or misaligned pointers, a connectivity
+ * other than 6 / 18 / 26, keep_largest outside 0..8, min_voxels < 0, a bad dimension, out
+ * overlapping mask: negative, no launch, outputs and work untouched.                        */
+int pcms_components_work_ints(int D, int H, int W);
+/* labels[i] = 0 on background, 1 + the smallest flat index of the voxel's component on
+ * foreground (predict.label_components): a function of the mask alone, deterministic.       */
+int pcms_components_label(const unsigned char* mask, int invert, int connectivity, int* labels, int* work, int D,
+                          int H, int W, hipStream_t s);
+/* predict.postprocess byte for byte: components ranked by (size descending, label ascending);
+ * one stays iff size >= min_voxels and (keep_largest == 0 or rank < keep_largest); then, with
+ * fill_holes != 0, every 6-connected background component that touches none of the six faces
+ * of the volume becomes 1.  out holds 0 / 1 bytes.                                           */
+int pcms_mask_postprocess(const unsigned char* mask, unsigned char* out, int* work, int keep_largest, int min_voxels,
+                          int fill_holes, int connectivity, int D, int H, int W, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

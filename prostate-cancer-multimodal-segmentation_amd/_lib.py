@@ -124,6 +124,9 @@ SIGNATURES = {
     "pcms_resample_linear_norm": "piiiiddppiiis",
     "pcms_flip_mean": "pippiiis",  # flipmask: a host pointer (ctypes.addressof)
     "pcms_prob_to_mask": "piiifppiiis",
+    "pcms_components_work_ints": "iii",
+    "pcms_components_label": "piippiiis",
+    "pcms_mask_postprocess": "pppiiiiiiis",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

@@ -164,6 +164,183 @@ def mask_on_grid(prob: np.ndarray, native_shape: Sequence[int], threshold: float
     return (prob_native > np.float32(threshold)).astype(np.uint8), prob_native
 
 
+# ---- mask post-processing ----------------------------------------------------------
+# Foreground is ``mask != 0``; the flat index of voxel (d, h, w) is ``(d*H + h)*W + w``; two voxels
+# are adjacent at ``connectivity`` 6 / 18 / 26 when every index offset is in {-1, 0, 1}, not all are
+# zero, and at most 1 / 2 / 3 of them are nonzero.
+MAX_KEEP_LARGEST = 8
+
+
+def _offsets(connectivity: int) -> List[Tuple[int, int, int]]:
+    if connectivity not in (6, 18, 26):
+        raise ValueError(f"connectivity is 6, 18 or 26, got {connectivity!r}")
+    most = {6: 1, 18: 2, 26: 3}[connectivity]
+    return [(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in (-1, 0, 1)
+            if 1 <= (a != 0) + (b != 0) + (c != 0) <= most]
+
+
+def _volume(mask) -> np.ndarray:
+    mask = np.asarray(mask)
+    if mask.ndim != 3 or 0 in mask.shape:
+        raise ValueError(f"a mask is a non-empty (D, H, W) volume, got shape {mask.shape}")
+    return mask
+
+
+def label_components(mask: np.ndarray, connectivity: int = 26) -> np.ndarray:
+    """Connected components of the foreground (``mask != 0``), int32 (D, H, W): 0 on background,
+    ``1 + the smallest flat index ((d*H + h)*W + w) of the voxel's component`` on foreground.
+    Adjacency at ``connectivity`` 6 / 18 / 26: offsets in {-1, 0, 1}, not all zero, at most
+    1 / 2 / 3 of them nonzero.  The label depends on the mask alone, never on a traversal order;
+    ranking the distinct labels in ascending order gives ``scipy.ndimage.label``'s numbering.
+    Computed by min-propagation over the shifted neighbours plus pointer jumping until nothing
+    changes: every voxel carries the flat index of its tree's root; a round takes the minimum
+    root over each voxel's neighbours, hangs every root below the smallest root seen by any of
+    its voxels, and jumps the pointers until every voxel points at a root again."""
+    offsets = _offsets(connectivity)
+    fg = _volume(mask) != 0
+    D, H, W = fg.shape
+    n = fg.size
+    big = np.int64(n)  # the background's value: larger than every index, so it never wins a minimum
+    fgi = np.flatnonzero(fg)
+    root = np.full(n, big, dtype=np.int64)  # root[i]: the root of voxel i's tree, a voxel with root[r] == r
+    root[fgi] = fgi
+    pad = np.full((D + 2, H + 2, W + 2), big, dtype=np.int64)
+    while True:
+        pad[1:-1, 1:-1, 1:-1] = root.reshape(fg.shape)
+        seen = pad[1:-1, 1:-1, 1:-1].copy()
+        for a, b, c in offsets:
+            np.minimum(seen, pad[1 + a:1 + a + D, 1 + b:1 + b + H, 1 + c:1 + c + W], out=seen)
+        seen = seen.reshape(-1)[fgi]
+        mine = root[fgi]
+        lower = seen < mine
+        if not lower.any():
+            break
+        np.minimum.at(root, mine[lower], seen[lower])  # a root hangs below a smaller root of its component
+        while True:  # pointer jumping
+            nxt = root[root[fgi]]
+            if np.array_equal(nxt, root[fgi]):
+                break
+            root[fgi] = nxt
+    lab = np.zeros(n, dtype=np.int32)
+    lab[fgi] = root[fgi] + 1
+    return lab.reshape(fg.shape)
+
+
+def _check_filter(keep_largest, min_voxels):
+    if not isinstance(keep_largest, (int, np.integer)) or not 0 <= keep_largest <= MAX_KEEP_LARGEST:
+        raise ValueError(f"keep_largest is an integer in 0..{MAX_KEEP_LARGEST}, got {keep_largest!r}")
+    if not isinstance(min_voxels, (int, np.integer)) or not 0 <= min_voxels < 2 ** 31:
+        raise ValueError(f"min_voxels is a non-negative 32-bit integer, got {min_voxels!r}")
+
+
+def filter_components(mask: np.ndarray, keep_largest: int = 0, min_voxels: int = 0,
+                      connectivity: int = 26) -> np.ndarray:
+    """The foreground (``mask != 0``) components that stay, as a uint8 0 / 1 mask.  All components
+    (``label_components`` at ``connectivity``) are ranked by (size descending, label ascending);
+    one stays iff ``size >= min_voxels`` and (``keep_largest == 0`` or its rank
+    ``< keep_largest``).  Equal sizes resolve to the smaller label.  ``keep_largest`` is in 0..8
+    and ``min_voxels >= 0``, else ValueError."""
+    _check_filter(keep_largest, min_voxels)
+    lab = label_components(mask, connectivity)
+    labels, inverse, sizes = np.unique(lab.reshape(-1), return_inverse=True, return_counts=True)
+    stay = (sizes >= min_voxels) & (labels != 0)
+    if keep_largest:
+        comp = np.flatnonzero(labels != 0)
+        order = comp[np.lexsort((labels[comp], -sizes[comp]))]  # size descending, then label ascending
+        top = np.zeros_like(stay)
+        top[order[:keep_largest]] = True
+        stay &= top
+    return stay[inverse.reshape(-1)].reshape(lab.shape).astype(np.uint8)
+
+
+def fill_holes(mask: np.ndarray) -> np.ndarray:
+    """``mask != 0`` with its enclosed holes filled, uint8: the background is labelled at
+    6-connectivity (always 6, the dual of 26 and ``scipy.ndimage.binary_fill_holes``' default) and
+    every background component with no voxel on any of the six faces of the volume becomes 1."""
+    fg = _volume(mask) != 0
+    lab = label_components(~fg, 6)
+    faces = np.concatenate([lab[0].ravel(), lab[-1].ravel(), lab[:, 0].ravel(), lab[:, -1].ravel(),
+                            lab[:, :, 0].ravel(), lab[:, :, -1].ravel()])
+    open_labels = np.unique(faces)
+    hole = (lab != 0) & ~np.isin(lab, open_labels)
+    return (fg | hole).astype(np.uint8)
+
+
+def postprocess(mask: np.ndarray, keep_largest: int = 0, min_voxels: int = 0, fill_holes: bool = False,
+                connectivity: int = 26) -> np.ndarray:
+    """``filter_components`` then (when asked) ``fill_holes``, uint8.  With ``keep_largest == 0``,
+    ``min_voxels <= 1`` and ``fill_holes=False`` this is ``(mask != 0)``."""
+    _check_filter(keep_largest, min_voxels)
+    _offsets(connectivity)
+    out = filter_components(mask, keep_largest, min_voxels, connectivity)
+    return _fill_holes(out) if fill_holes else out
+
+
+_fill_holes = fill_holes  # postprocess's keyword of the same name shadows the function there
+
+
+def _device_mask(mask, what: str) -> torch.Tensor:
+    if not isinstance(mask, torch.Tensor) or mask.device.type != "cuda":
+        where = mask.device if isinstance(mask, torch.Tensor) else type(mask).__name__
+        raise RuntimeError(f"{what} needs a uint8 tensor on the GPU, not '{where}': pcms_amd has no CPU fallback -- "
+                           "use the host form of the same name without _device")
+    if mask.dtype != torch.uint8 or mask.dim() != 3 or mask.numel() == 0:
+        raise ValueError(f"{what} takes a non-empty uint8 (D, H, W) tensor, got {mask.dtype} {tuple(mask.shape)}")
+    return mask.contiguous()
+
+
+def _components_work(mask: torch.Tensor) -> torch.Tensor:
+    from ._lib import query
+    n = query("pcms_components_work_ints", *mask.shape)
+    if n < 0:
+        raise ValueError(f"a volume of shape {tuple(mask.shape)} is too large to label")
+    return torch.empty(n, dtype=torch.int32, device=mask.device)
+
+
+def _check_status(status: int, what: str) -> None:
+    if status != 0:
+        raise RuntimeError(f"{what}: a labelling kernel ran into its iteration cap (status {status})")
+
+
+def _postprocess_enqueue(mask: torch.Tensor, keep_largest, min_voxels, fill_holes, connectivity):
+    """(out, work) with pcms_mask_postprocess enqueued on the current stream; work[0] is the
+    status the caller copies back with the mask."""
+    from ._lib import call
+    _check_filter(keep_largest, min_voxels)
+    _offsets(connectivity)
+    out = torch.empty_like(mask)
+    work = _components_work(mask)
+    call("pcms_mask_postprocess", mask, out, work, int(keep_largest), int(min_voxels), int(bool(fill_holes)),
+         int(connectivity), *mask.shape)
+    return out, work
+
+
+def postprocess_device(mask: torch.Tensor, keep_largest: int = 0, min_voxels: int = 0, fill_holes: bool = False,
+                       connectivity: int = 26) -> torch.Tensor:
+    """``postprocess`` on the GPU, byte for byte: a uint8 CUDA tensor (D, H, W) in, a new uint8
+    tensor out, enqueued on the current stream (pcms_mask_postprocess).  The kernels' status word
+    is read back at the end; RuntimeError if it is nonzero.  A CPU tensor raises."""
+    mask = _device_mask(mask, "postprocess_device")
+    with torch.cuda.device(mask.device):
+        out, work = _postprocess_enqueue(mask, keep_largest, min_voxels, fill_holes, connectivity)
+        _check_status(int(work[0].item()), "postprocess_device")
+    return out
+
+
+def label_components_device(mask: torch.Tensor, connectivity: int = 26, invert: bool = False) -> torch.Tensor:
+    """``label_components`` on the GPU, bit for bit (pcms_components_label): int32 (D, H, W), the
+    lesion map.  ``invert=True`` labels the zero voxels instead.  A CPU tensor raises."""
+    from ._lib import call
+    mask = _device_mask(mask, "label_components_device")
+    _offsets(connectivity)
+    with torch.cuda.device(mask.device):
+        labels = torch.empty(mask.shape, dtype=torch.int32, device=mask.device)
+        work = _components_work(mask)
+        call("pcms_components_label", mask, int(bool(invert)), int(connectivity), labels, work, *mask.shape)
+        _check_status(int(work[0].item()), "label_components_device")
+    return labels
+
+
 def _flip_masks(flips) -> List[int]:
     """Flip sets (tuples of axes out of 0, 1, 2) as pcms_flip_mean's bit masks, () first."""
     masks = [0]
@@ -258,7 +435,8 @@ class ModelPredictor:
     def predict_case(self, case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
                      handle_missing: str = "zero_fill", normalise: bool = True, threshold: float = 0.5,
                      tta_flips: Sequence[Tuple[int, ...]] = (), output_like: Optional[str] = None,
-                     return_probability: bool = False) -> CasePrediction:
+                     return_probability: bool = False, *, keep_largest: int = 0, min_voxels: int = 0,
+                     fill_holes: bool = False, connectivity: int = 26) -> CasePrediction:
         """One case from its raw NIfTI files to a mask on its native grid, on the GPU:
         ``prepare_case_device`` -> the network on the input and on its copies flipped along each
         of ``tta_flips`` (tuples of axes out of 0, 1, 2) in one batch -> pcms_flip_mean
@@ -266,9 +444,15 @@ class ModelPredictor:
         of the mask to the host (and of the probabilities with ``return_probability``).  The
         native grid is that of ``output_like`` (any NIfTI file, e.g. the label) or else of the
         first present modality's file.  ``normalise=False`` feeds the network what the training
-        loader feeds it; ``normalise=True`` what ``load_multimodal_images`` would, resampled."""
+        loader feeds it; ``normalise=True`` what ``load_multimodal_images`` would, resampled.
+        ``keep_largest`` / ``min_voxels`` / ``fill_holes`` / ``connectivity`` (keyword-only): the
+        mask goes through pcms_mask_postprocess (``postprocess``) on the device before the copy;
+        with their defaults nothing is launched for them."""
         from ._lib import call
         masks = _flip_masks(tta_flips)
+        _check_filter(keep_largest, min_voxels)
+        _offsets(connectivity)
+        post = keep_largest != 0 or min_voxels > 1 or bool(fill_holes)
         x = prepare_case_device(case_dir, target_size, handle_missing, normalise, self.device)  # raises if none present
         reference = output_like if output_like is not None else \
             next(p for p in _case_files(case_dir) if p is not None)
@@ -287,6 +471,13 @@ class ModelPredictor:
             mask = torch.empty(native, dtype=torch.uint8, device=self.device)
             prob_native = torch.empty(native, dtype=torch.float32, device=self.device) if return_probability else None
             call("pcms_prob_to_mask", prob, *grid, float(threshold), mask, prob_native, *native)
+            if post:
+                mask, work = _postprocess_enqueue(mask, keep_largest, min_voxels, fill_holes, connectivity)
+                # the status word travels with the mask: one device-to-host copy
+                both = torch.cat([mask.reshape(-1), work[:1].view(torch.uint8)]).cpu().numpy()
+                _check_status(int.from_bytes(both[-4:].tobytes(), "little", signed=True), "predict_case")
+                return CasePrediction(both[:-4].reshape(native),
+                                      prob_native.cpu().numpy() if return_probability else None, reference, geometry)
         return CasePrediction(mask.cpu().numpy(), prob_native.cpu().numpy() if return_probability else None,
                               reference, geometry)
 
