@@ -10,7 +10,8 @@ Layout: activations NDHWC in ``dtype`` (bf16 default, fp32 parity build); parame
 in ONE flat fp32 master buffer (the module's nn.Parameters are views into it, so
 ``state_dict()`` keys/shapes are the reference's), gradients in one flat fp32 buffer
 (``param.grad`` views), BatchNorm running stats in one flat fp32 buffer.  Kernel weight
-packs (bf16 / fp32, MFMA-friendly order) are rebuilt from the master when it changes.
+packs (bf16 / fp32, MFMA-friendly order) are rebuilt from the master when it changes: they
+and the rule that keeps them current live in packs.WeightPacks (``self.packs``).
 
 The engine keeps the activations of the LAST training forward; ``backward`` must follow
 that forward (checked).  ``backward(dlogits, want_dx=True)`` also returns the gradient of the
@@ -30,8 +31,8 @@ import torch
 from . import _lib
 from ._lib import BF16, F32, F32X3, call, query
 from .dp import module_grad_ranges
+from .packs import BN_EPS, WeightPacks, gaps
 
-BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
 
 _DT = {"bf16": (torch.bfloat16, BF16), "fp32": (torch.float32, F32)}
@@ -74,23 +75,18 @@ class Layout(NamedTuple):
 
 
 class ConvSpec:
-    __slots__ = ("mod", "cin", "cout", "cin_store", "fwd", "dgrad", "code", "fwd16", "dgrad16", "old_stale",
-                 "old_used", "i")
+    __slots__ = ("mod", "cin", "cout", "cin_store", "fwd", "dgrad", "code", "fwd16", "dgrad16", "i")
 
     def __init__(self, mod, cin, cout, cin_store):
         self.mod, self.cin, self.cout, self.cin_store = mod, cin, cout, cin_store
         self.i = None  # index in UNetEngine.convs (and in Layout.fwd / .dgrad)
+        # the weight packs, allocated and kept current by packs.WeightPacks: the general
+        # kernel's pair, and the pcms_conv3_pack16 forms for the 16x16x32 big-box kernel
+        # (pcms_conv3_fwd16) where the forward / dgrad can run on it at the allocated shape
         self.fwd = None
         self.dgrad = None
-        # pcms_conv3_pack16 forms for the 16x16x32 big-box kernel (pcms_conv3_fwd16), set by
-        # UNetEngine._alloc for the convs whose forward / dgrad run on it at the allocated shape
         self.fwd16 = None
         self.dgrad16 = None
-        # fwd / dgrad (the general kernel's packs) not rewritten by the last fused Adam (it
-        # writes only the pack16 forms of a conv whose every call at the allocated shape ran
-        # on the 16x16x32 kernel); old_used: a call at this shape needed them
-        self.old_stale = False
-        self.old_used = False
         # conv-kernel dtype code: BF16, or for fp32 data F32 (bf16x6 arithmetic, fp32-grade)
         # / F32X3 (bf16x3, faster, ~10x the fp32 rounding error)
         self.code = None
@@ -153,7 +149,6 @@ class UNetEngine:
             self.bns += [b.b0, b.b1]
         for i, cs in enumerate(self.convs):
             cs.code, cs.i = self.code, i
-        self.convt_packs: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
         # bf16 build: the stem runs on dedicated tap-packed kernels (HBM-bound)
         self.stem_fast = self.code == BF16 and self.cp == 8
         self.stem_sup = 0  # pcms_stem_supported bits for the allocated shape (set by _alloc)
@@ -169,19 +164,8 @@ class UNetEngine:
         # (pcms_conv3_fwd16, pack16 weights rebuilt with the other packs); PCMS_B16=0 keeps the
         # 32x32x16 big-box kernel (A/B)
         self.use_b16 = os.environ.get("PCMS_B16", "1") != "0"
-        self._p16 = None  # pcms_conv3_pack16 table for the allocated shape
-        self.stem_pack = None
-        # pcms_stem_dgrad's weight pack (the input gradient): built from the master on first
-        # use and again when the weights moved on (_stem_dgrad), so a step that asks for no
-        # input gradient launches and allocates nothing for it
-        self.stem_dpack = None
-        self._stem_dpack_key = None
+        self.packs = WeightPacks(self)
         self._flat_ptrs = None
-        self._packed_version = -1
-        self._dirty = True
-        self._packs_fresh = False  # the fused Adam wrote every conv / ConvT pack (not the stem's)
-        self._stem_conv_stale = False  # the stem's general-kernel pack skipped by the fast path
-        self._adam_plan = None
         # the settings below (with fuse_bnin / use_b16 above) are read once per forward, into the
         # allocation key (forward()); everything after follows self.layout, the plan _alloc made
         # from them, so a change takes effect at the next forward
@@ -227,13 +211,7 @@ class UNetEngine:
         # applied in the conv epilogue (PCMS_CONV_RELU): conv -> BN -> ReLU is one pass
         # (models/unet3d.py:298-344 predict / inference).  False: the unfolded eval path.
         self.fold_bn_eval = True
-        self._eval = None      # {conv index: (fwd pack, folded bias)}, "stem": stem pack
-        self._eval_key = None
         self._bn_epoch = 0     # training forwards so far (each moves the running statistics)
-        # weight generation: bumped by every change of the master weights the storage version
-        # counter does not see (the fused Adam writes flat_p through the C-ABI), by
-        # re-flattening and by a change of conv arithmetic; part of the eval-pack key
-        self._wgen = 0
         self._store_ranges = None  # (stem_sup, fill plan) of _store_plan
         self._gstore = False       # this backward writes conv weight gradients (PCMS_GRAD_STORE)
         self._flatten()
@@ -247,14 +225,10 @@ class UNetEngine:
         if self.code == BF16:
             raise ValueError("the bf16 build has one conv arithmetic")
         code = {"x6": F32, "x3": F32X3}[mode]
-        for i, cs in enumerate(self.convs):
-            if convs is None or i in convs:
-                cs.code = code
-                cs.fwd = cs.dgrad = None
-        self._dirty = True
-        self._wgen += 1
-        self._adam_plan = None  # its table holds the old packs' pointers
-        self._eval = None
+        changed = [cs for cs in self.convs if convs is None or cs.i in convs]
+        for cs in changed:
+            cs.code = code
+        self.packs.recoded(changed)
         self.buf_key = None
 
     # ------------------------------------------------------------------ parameters
@@ -290,11 +264,8 @@ class UNetEngine:
         self.params = params
         self.flat_p, self.flat_g, self.flat_bn = flat, gflat, bflat
         self._flat_ptrs = [p.data_ptr() for p in params]
-        self._dirty = True
-        self._wgen = getattr(self, "_wgen", 0) + 1
-        self._adam_plan = None
+        self.packs.rebased()
         self._store_ranges = None  # offsets into the new flat buffer
-        self._p16 = None           # weight pointers of the pack16 table
         self.grad_ranges = module_grad_ranges(self.model)
         # [lo, hi) of every parameter in the flat gradient (per-layer readiness for dp.GradSync)
         self.param_span = {}
@@ -400,238 +371,41 @@ class UNetEngine:
         key = self.stem_sup
         if self._store_ranges is not None and self._store_ranges[0] == key:
             return self._store_ranges[1]
-        base = self.flat_g.data_ptr()
         stored = []
         for i, cs in enumerate(self.convs):
             if i == 0 and self.stem_sup & 2:
                 continue  # the stem's streaming kernel accumulates
             w = cs.mod.weight
             stored.append(((w.data_ptr() - self.flat_p.data_ptr()) // 4, w.numel()))
-        ranges, pos = [], 0
-        for off, n in sorted(stored):
-            if off > pos:
-                ranges.append([pos, off])
-            pos = off + n
-        if pos < self.flat_g.numel():
-            ranges.append([pos, self.flat_g.numel()])
+        ranges = gaps(stored, self.flat_g.numel())
         plan = (torch.tensor(ranges, dtype=torch.int64, device=self.device), len(ranges),
                 max(e - b for b, e in ranges))
         self._store_ranges = (key, plan)
         return plan
 
     def mark_dirty(self, packs_fresh: bool = False):
-        """The master weights changed.  ``packs_fresh``: the fused Adam (adam_plan) already
-        wrote the conv and ConvT packs from the new weights; only the stem's remain."""
-        self._dirty = True
-        self._wgen += 1
-        self._packs_fresh = packs_fresh and self._packed_version == self.flat_p._version
-        if self._packs_fresh and self._adam_plan is not None:
-            for cs in self._adam_plan["old_skip"]:
-                cs.old_stale = True
+        """The master weights changed.  ``packs_fresh``: by a fused Adam step (adam_plan), which
+        already wrote its plan's packs from the new weights."""
+        self.packs.changed(by_plan=packs_fresh)
+
+    # ------------------------------------------------------------------ weight packs (packs.WeightPacks)
+    stem_pack = property(lambda self: self.packs.stem)
+    convt_packs = property(lambda self: self.packs.convt)
 
     def adam_plan(self):
-        """Fused Adam + weight-pack plan (FlatAdam.step): device tables of the conv / ConvT
-        weights whose packs the Adam kernels write (int64 rows, see include/pcms_hip.h
-        pcms_adam_pack_conv3) and the [begin, end) ranges of every other parameter.  The bf16
-        build writes bf16 packs; the fp32 build (``"x6"``: True) its bf16x6 packs, for the
-        convs in bf16x6 mode (a conv switched to bf16x3 is repacked as before)."""
-        if self._adam_plan is not None:
-            return self._adam_plan
-        x6 = self.code != BF16
-        self._ensure_packs()
-        base = self.flat_p.data_ptr()
-
-        def offset(t):
-            return (t.data_ptr() - base) // 4
-
-        fused = []
-        skipped = 0  # layers (besides the stem) whose packs the Adam kernels do not write
-        conv_rows, tiles, old_skip = [], 0, []
-        for i, cs in enumerate(self.convs):
-            w = cs.mod.weight
-            if i == 0:
-                continue
-            if cs.cin % 32 or cs.cout % 32 or offset(w) % 4 or (x6 and cs.code != F32):
-                skipped += 1
-                continue
-            # bf16 build: the pack16 forms too; the general kernel's packs only where a call
-            # at this shape used them (else marked stale, repacked on first use: _old_packs)
-            f16 = cs.fwd16.data_ptr() if not x6 and cs.fwd16 is not None else 0
-            d16 = cs.dgrad16.data_ptr() if not x6 and cs.dgrad16 is not None else 0
-            skip = bool(f16 and d16) and not cs.old_used
-            conv_rows.append([offset(w), cs.cout, cs.cin, 0 if skip else cs.fwd.data_ptr(),
-                              0 if skip else cs.dgrad.data_ptr(), tiles, f16, d16])
-            if skip:
-                old_skip.append(cs)
-            tiles += (cs.cout // 32) * (cs.cin // (16 if x6 else 32))
-            fused.append((offset(w), w.numel()))
-        ct_rows, ct_tiles = [], 0
-        for i, up in enumerate(self.ups):
-            w = up.weight
-            cin, cout = up.in_channels, up.out_channels
-            if cin % 32 or cout % 32 or offset(w) % 4:
-                skipped += 1
-                continue
-            f, d = self.convt_packs[i]
-            ct_rows.append([offset(w), cin, cout, f.data_ptr(), d.data_ptr(), ct_tiles, 0, 0])
-            ct_tiles += (cin // 32) * (cout // 32)
-            fused.append((offset(w), w.numel()))
-        ranges, pos = [], 0
-        for off, n in sorted(fused):
-            if off > pos:
-                ranges.append([pos, off])
-            pos = off + n
-        if pos < self.flat_p.numel():
-            ranges.append([pos, self.flat_p.numel()])
-        dev = self.device
-
-        def tab(rows):
-            return torch.tensor(rows if rows else [[0] * 8], dtype=torch.int64, device=dev)
-        self._adam_plan = {
-            "conv": tab(conv_rows), "nconv": len(conv_rows), "conv_tiles": tiles,
-            "convt": tab(ct_rows), "nconvt": len(ct_rows), "convt_tiles": ct_tiles,
-            "ranges": torch.tensor(ranges if ranges else [[0, 0]], dtype=torch.int64, device=dev),
-            "nranges": len(ranges), "max_len": max([e - b for b, e in ranges], default=0),
-            # every conv / ConvT pack but the stem's comes out of the Adam pass (else the step
-            # must not mark the packs fresh: a skipped layer would train on stale packs)
-            "complete": skipped == 0,
-            "x6": x6,
-            "old_skip": old_skip,  # convs whose general-kernel packs this plan does not write
-            "p16": not x6,         # the pack16 forms come out of the Adam pass
-        }
-        return self._adam_plan
+        return self.packs.adam_plan()
 
     def _ensure_packs(self):
-        v = self.flat_p._version
-        if not self._dirty and v == self._packed_version:
-            return
-        if self._packs_fresh and v == self._packed_version:
-            # the fused Adam rewrote every conv / ConvT pack: only the stem's are left.  With
-            # the direct stem kernels its general-kernel pack is needed only by a shape they do
-            # not run (packed on first use there: _conv)
-            cs = self.convs[0]
-            if self.stem_fast:
-                call("pcms_stem_pack", cs.mod.weight, self.stem_pack, self.nmod)
-                self._stem_conv_stale = True
-            elif cs.dgrad is None:
-                call("pcms_conv3_pack", cs.code, cs.mod.weight, cs.fwd, cs.cout, cs.cin, 0)
-            else:
-                call("pcms_conv3_pack2", cs.code, cs.mod.weight, cs.fwd, cs.dgrad, cs.cout, cs.cin)
-            self._dirty = False
-            self._packs_fresh = False
-            if self._adam_plan is None or not self._adam_plan["p16"]:
-                self._pack16()
-            return
-        for i, cs in enumerate(self.convs):
-            w = cs.mod.weight
-            if cs.fwd is None:
-                cs.fwd = torch.empty(query("pcms_conv3_pack_elems", cs.code, cs.cout, cs.cin), dtype=self.tdtype,
-                                     device=self.device)
-                if i != 0:  # the stem's input needs no gradient -> no dgrad pack
-                    cs.dgrad = torch.empty(query("pcms_conv3_pack_elems", cs.code, cs.cin, cs.cout),
-                                           dtype=self.tdtype, device=self.device)
-            if cs.dgrad is not None:
-                call("pcms_conv3_pack2", cs.code, w, cs.fwd, cs.dgrad, cs.cout, cs.cin)
-            else:
-                call("pcms_conv3_pack", cs.code, w, cs.fwd, cs.cout, cs.cin, 0)
-        if self.stem_fast:
-            if self.stem_pack is None:
-                self.stem_pack = torch.empty(query("pcms_stem_pack_elems"), dtype=self.tdtype, device=self.device)
-            call("pcms_stem_pack", self.convs[0].mod.weight, self.stem_pack, self.nmod)
-        for i, up in enumerate(self.ups):
-            cin, cout = up.in_channels, up.out_channels
-            if i not in self.convt_packs:
-                n = query("pcms_convt_pack_elems", self.code, cin, cout)
-                self.convt_packs[i] = (torch.empty(n, dtype=self.tdtype, device=self.device),
-                                       torch.empty(n, dtype=self.tdtype, device=self.device))
-            f, d = self.convt_packs[i]
-            call("pcms_convt_pack", self.code, up.weight, f, cin, cout, 0)
-            call("pcms_convt_pack", self.code, up.weight, d, cin, cout, 1)
-        for cs in self.convs:
-            cs.old_stale = False
-        self._packed_version = self.flat_p._version
-        self._dirty = False
-        self._packs_fresh = False
-        self._stem_conv_stale = False
-        self._pack16()
-
-    def _pack16(self):
-        """The pack16 forms of the convs running on the 16x16x32 big-box kernel at the allocated
-        shape: one batched pcms_conv3_pack16 launch from the fp32 master (its table is rebuilt
-        when the buffers or the flat parameters move)."""
-        if self._p16 is None:
-            rows, tiles = [], 0
-            for cs in self.convs:
-                if cs.fwd16 is None and cs.dgrad16 is None:
-                    continue
-                rows.append([cs.mod.weight.data_ptr(), cs.cout, cs.cin, 0 if cs.fwd16 is None else cs.fwd16.data_ptr(),
-                             0 if cs.dgrad16 is None else cs.dgrad16.data_ptr(), tiles, 0, 0])
-                tiles += (cs.cout // 32) * (cs.cin // 32)
-            self._p16 = (torch.tensor(rows if rows else [[0] * 8], dtype=torch.int64, device=self.device), len(rows),
-                         tiles)
-        tab, n, tiles = self._p16
-        if n:
-            call("pcms_conv3_pack16", tab, n, tiles)
-
-    def _old_packs(self, cs: ConvSpec):
-        """The general kernel's packs of ``cs`` before a call that reads them: rebuilt from the
-        master when the fused Adam skipped them, and the Adam plan redone so that it writes
-        them from the next step on."""
-        if cs.old_stale:
-            call("pcms_conv3_pack2", cs.code, cs.mod.weight, cs.fwd, cs.dgrad, cs.cout, cs.cin)
-            cs.old_stale = False
-        if not cs.old_used:
-            cs.old_used = True
-            self._adam_plan = None
-
-    def _stem_conv_pack(self):
-        """The stem conv's general-kernel weight pack, when the fast path skipped it."""
-        if self._stem_conv_stale:
-            cs = self.convs[0]
-            if cs.dgrad is None:
-                call("pcms_conv3_pack", cs.code, cs.mod.weight, cs.fwd, cs.cout, cs.cin, 0)
-            else:
-                call("pcms_conv3_pack2", cs.code, cs.mod.weight, cs.fwd, cs.dgrad, cs.cout, cs.cin)
-            self._stem_conv_stale = False
-
-    def _ensure_eval_packs(self):
-        """Folded eval weights: w' = w * gamma / sqrt(rvar + eps), b' = b * sc + beta - rmean * sc
-        per conv (pcms_bn_fold, then the forward pack of w'); rebuilt when the parameters or
-        the running statistics changed."""
-        self._ensure_packs()
-        key = (self._wgen, self.flat_p._version, self.flat_bn._version, self._bn_epoch)
-        if self._eval is not None and self._eval_key == key:
-            return
-        if self._eval is None:
-            self._eval = {}
-            big = max(cs.cout * cs.cin * 27 for cs in self.convs)
-            self._eval_tmp = torch.empty(big, dtype=torch.float32, device=self.device)
-        tmp = self._eval_tmp
-        for i, (cs, bn) in enumerate(zip(self.convs, self.bns)):
-            if i not in self._eval:
-                self._eval[i] = (torch.empty(query("pcms_conv3_pack_elems", cs.code, cs.cout, cs.cin),
-                                             dtype=self.tdtype, device=self.device),
-                                 torch.empty(cs.cout, dtype=torch.float32, device=self.device))
-            pack, bias = self._eval[i]
-            m = bn.mod
-            call("pcms_bn_fold", cs.mod.weight, cs.mod.bias, m.weight, m.bias, m.running_mean, m.running_var,
-                 BN_EPS, cs.cout, cs.cin * 27, tmp, bias)
-            call("pcms_conv3_pack", cs.code, tmp, pack, cs.cout, cs.cin, 0)
-            if i == 0 and self.stem_fast:
-                if "stem" not in self._eval:
-                    self._eval["stem"] = torch.empty(query("pcms_stem_pack_elems"), dtype=self.tdtype,
-                                                     device=self.device)
-                call("pcms_stem_pack", tmp, self._eval["stem"], self.nmod)
-        self._eval_key = key
+        self.packs.ensure()
 
     def _conv_eval(self, i: int, x0, c0, x1, c1, a, N, S):
         """a = relu(conv'(x) + b'): the folded eval conv of self.convs[i] (no statistics)."""
         cs = self.convs[i]
-        pack, bias = self._eval[i]
+        pack, bias = self.packs.eval[i]
         RELU = 2  # PCMS_CONV_RELU
         r = self.layout.fwd[i]  # the stem kernel or the general one, whatever the training route
         if r.kind == "stem":
-            call("pcms_stem_fwd", x0, self._eval["stem"], bias, a, None, N, *S, RELU | self.stem_dense)
+            call("pcms_stem_fwd", x0, self.packs.eval["stem"], bias, a, None, N, *S, RELU | self.stem_dense)
         elif r.splits == 1:
             call("pcms_conv3_fwd", cs.code, x0, c0, x1, c1, pack, bias, a, None, cs.cout, None, None, RELU,
                  N, *S, cs.cout, 1)
@@ -750,18 +524,11 @@ class UNetEngine:
             fwd.append(self._route(N, S[l], c0, c1, cs.cout, cs.code, b16 and not stem,
                                    stem=stem and bool(self.stem_sup & 1), bnin=cs.i % 2 == 1 and bnin[cs.i // 2]))
             dgrad.append(None if stem else self._route(N, S[l], cs.cout, 0, cs.cin, cs.code, b16, dgrad=True))
-            # the 16x16x32 kernel's weight forms, where it can run the layer
-            cs.fwd16 = cs.dgrad16 = None
-            if fwd[-1].pack16:
-                cs.fwd16 = torch.empty(query("pcms_conv3_pack16_elems", cs.cout, cs.cin), dtype=T, device=dev)
-            if dgrad[-1] is not None and dgrad[-1].pack16:
-                cs.dgrad16 = torch.empty(query("pcms_conv3_pack16_elems", cs.cin, cs.cout), dtype=T, device=dev)
             # both split forms of either direction, whichever the route takes (_conv_eval always
             # takes the general one)
             for r, cout in ((fwd[-1], cs.cout), (dgrad[-1], cs.cin)):
                 if r is not None:
                     yacc = max(yacc, (r.slabs if r.splits > 1 else 0) * nv[l] * cout, r.slabs16 * nv[l] * cout)
-            cs.old_used = False
         rows_s = max(query("pcms_split_epilogue_rows", nv[l]) for l in range(5))
         rows_b = max(query("pcms_bn_bwd_rows", self.code, C[l], nv[l]) for l in range(5))
         # BN partials [rows][C][2] + [rows] voxel counts
@@ -794,10 +561,7 @@ class UNetEngine:
         ctws += [query("pcms_convt_fwd_ws_floats", N, *S[4 - i], up.in_channels, up.out_channels)
                  for i, up in enumerate(self.ups)]
         b["ctws"] = torch.empty(max(ctws), dtype=torch.float32, device=dev)
-        self._p16 = None
-        self._dirty = True  # build the new pack16 forms before the next conv
-        self._packs_fresh = False  # (those of the last fused Adam went to the old buffers)
-        self._adam_plan = None
+        self.packs.relaid(fwd, dgrad)  # the 16x16x32 kernel's weight forms, where it can run the layer
         self.bufs = b
         self.buf_key = key
         self.layout = L._replace(fwd=tuple(fwd), dgrad=tuple(dgrad), bnin=bnin, pool_rows=pool_rows)
@@ -841,9 +605,7 @@ class UNetEngine:
             call("pcms_conv3_fwd16_split", x0, c0, x1, c1, pack16, acc, N, *S, cout, r.slabs16)
             call("pcms_split_epilogue", self.code, acc, r.slabs16, bias, y0, y1, cy0, st, cout, nvox, 0)
         else:  # the general kernel and its packs (rebuilt here when the fused Adam skipped them)
-            if cs.i == 0:
-                self._stem_conv_pack()
-            self._old_packs(cs)
+            self.packs.general(cs)
             if bnin is not None:
                 call("pcms_conv3_fwd_bnin", cs.code, x0, c0, isc, ish, pack, bias, y0, st, N, *S, cout)
             elif r.kind == "gen":
@@ -938,7 +700,7 @@ class UNetEngine:
             x = x.float()
         N, _, D, H, W = x.shape
         # buffers first: a (re)allocation decides which convs run on the 16x16x32 kernel and
-        # marks the packs dirty, so their pack16 forms are built by the _ensure_packs below.
+        # gives them new pack16 buffers, which the _ensure_packs below fills.
         # The one read of the step's settings and of the library's switches: the key
         key = (N, D, H, W, self.act_ckpt, self.wgrad_side_min_level, self.convt_wgrad_side, self.pool_bn_apply_fused,
                self.wgrad_target, self.split_target, self.fuse_bnin, self.use_b16, _lib.switches())
@@ -947,7 +709,7 @@ class UNetEngine:
         self._ensure_packs()
         folded = self._folded = not training and self.fold_bn_eval and not keep_input_grad
         if folded:
-            self._ensure_eval_packs()
+            self.packs.ensure_eval()
         else:
             self._bn_epoch += training
         b = self.bufs
@@ -993,16 +755,10 @@ class UNetEngine:
     def _stem_dgrad(self, dy1, N, S) -> torch.Tensor:
         """dx (N, n_modalities, D, H, W) fp32 = the stem conv's input gradient of ``dy1`` (the
         gradient of its pre-BN output), on the current stream."""
-        key = (self._wgen, self.flat_p._version)
-        if self.stem_dpack is None:
-            self.stem_dpack = torch.empty(query("pcms_stem_dgrad_pack_elems", self.code), dtype=self.tdtype,
-                                          device=self.device)
-        if key != self._stem_dpack_key:
-            call("pcms_stem_dgrad_pack", self.code, self.convs[0].mod.weight, self.stem_dpack, self.nmod)
-            self._stem_dpack_key = key
+        dpack = self.packs.stem_dgrad_pack()
         dx = torch.empty((N, self.nmod, *S), dtype=torch.float32, device=self.device)
         with self._timed("stem_dgrad"):
-            call("pcms_stem_dgrad", self.code, dy1, self.stem_dpack, dx, N, *S, self.nmod)
+            call("pcms_stem_dgrad", self.code, dy1, dpack, dx, N, *S, self.nmod)
         return dx
 
     def _block_bwd(self, blk: BlockSpec, ga2, acts, x0, c0, x1, c1, gx_out0, gx_out1, cy0, N, S, lvl,

@@ -179,7 +179,7 @@ def test_fused_adam_packs_match_flat_adam(gscale, precision):
         opt.step()
         eng = m.engine()
         eng._ensure_packs()
-        eng._stem_conv_pack()  # the stem's general-kernel pack is otherwise built on first use
+        eng.packs.general(eng.convs[0])  # the stem's general-kernel pack is otherwise built on first use
         torch.cuda.synchronize()
         runs.append((eng, opt))
     (e0, o0), (e1, o1) = runs
@@ -190,7 +190,8 @@ def test_fused_adam_packs_match_flat_adam(gscale, precision):
         torch.testing.assert_close(b, a, rtol=1e-6, atol=1e-12)
     # (the general kernel's packs of convs that run only on the 16x16x32 kernel are skipped
     # by the fused Adam and rebuilt on use: test_fused_adam_writes_pack16)
-    packs = [(t, t.clone()) for cs in e1.convs if not cs.old_stale for t in (cs.fwd, cs.dgrad) if t is not None]
+    packs = [(t, t.clone()) for cs in e1.convs if e1.packs.current(("gen", cs.i)) for t in (cs.fwd, cs.dgrad)
+             if t is not None]
     packs += [(t, t.clone()) for i in range(4) for t in e1.convt_packs[i]]
     packs += [(t, t.clone()) for cs in e1.convs for t in (cs.fwd16, cs.dgrad16) if t is not None]
     assert len(packs) >= 21
@@ -206,7 +207,7 @@ def test_fused_adam_writes_pack16():
     """At a shape where the 16x16x32 kernel runs (1 x 5x128x128x64), the fused Adam also writes
     the pack16 forms (no separate pcms_conv3_pack16 pass) and skips the general kernel's packs
     of the convs no call used; both are bit-identical to the pack kernels run on the updated
-    master, and a skipped pack is rebuilt on first use (engine._old_packs), which re-plans."""
+    master, and a skipped pack is rebuilt on first use (packs.WeightPacks.general), which re-plans."""
     from pcms_amd.models.unet3d import UNet3D
     from pcms_amd.optim import FlatAdam
     from pcms_amd.utils.losses import BCEDiceLoss
@@ -221,17 +222,18 @@ def test_fused_adam_writes_pack16():
         BCEDiceLoss()(m(x), y).backward()
         opt.step()
     eng = m.engine()
-    plan = eng._adam_plan
+    pk = eng.packs
+    plan = pk._plan
     assert plan is not None and plan["p16"] and plan["complete"]
     with16 = [cs for cs in eng.convs if cs.fwd16 is not None or cs.dgrad16 is not None]
     assert len(with16) >= 8
-    assert plan["old_skip"] and all(cs.old_stale for cs in plan["old_skip"])
+    assert plan["skipped"] and not any(pk.current(("gen", i)) for i in plan["skipped"])
     p16 = [t.clone() for cs in with16 for t in (cs.fwd16, cs.dgrad16) if t is not None]
-    old = {id(cs): (cs.fwd.clone(), cs.dgrad.clone()) for cs in eng.convs[1:] if not cs.old_stale}
+    old = {id(cs): (cs.fwd.clone(), cs.dgrad.clone()) for cs in eng.convs[1:] if pk.current(("gen", cs.i))}
     # a skipped pack, rebuilt on use
-    cs = plan["old_skip"][0]
-    eng._old_packs(cs)
-    assert not cs.old_stale and cs.old_used and eng._adam_plan is None
+    cs = eng.convs[plan["skipped"][0]]
+    pk.general(cs)
+    assert pk.current(("gen", cs.i)) and cs.i in pk.read and pk._plan is None
     lazy = (cs.fwd.clone(), cs.dgrad.clone())
     eng.mark_dirty()
     eng._ensure_packs()  # full repack (general packs + pcms_conv3_pack16) from the same master
