@@ -504,6 +504,34 @@ int pcms_components_label(const unsigned char* mask, int invert, int connectivit
 int pcms_mask_postprocess(const unsigned char* mask, unsigned char* out, int* work, int keep_largest, int min_voxels,
                           int fill_holes, int connectivity, int D, int H, int W, hipStream_t s);
 
+/* ---- surface distances: predict.py's surface / edt_sq / surface_metrics on the device ------ */
+/* Volumes are (D, H, W) with W fastest; foreground / feature is byte != 0.  Every axis is at
+ * most 2048 long (the H and D passes stage whole lines in LDS) and the volume at most
+ * 2^30 - 4096 voxels; pcms_edt_work_bytes(D, H, W) is the bytes of device workspace all three
+ * entry points accept (8-byte aligned), negative for a dimension < 1 or a volume past those
+ * limits.  Everything is enqueued on s: no allocation, no host synchronisation.  A NULL or
+ * misaligned pointer, a bad dimension, a spacing that is not finite and > 0, an output or the
+ * workspace overlapping an input or one another: negative, no launch, outputs and work untouched. */
+int pcms_edt_work_bytes(int D, int H, int W);
+/* out[i] = 1 where voxel i is foreground and one of its six face neighbours is background or
+ * lies outside the volume, else 0 (predict.surface).                                          */
+int pcms_mask_surface(const unsigned char* mask, unsigned char* out, int D, int H, int W, hipStream_t s);
+/* predict.edt_sq bit for bit: out[p] (fp64) = min over feature voxels q of
+ * fl(Z(|pd-qd|) + fl(Y(|ph-qh|) + X(|pw-qw|))), X(k) = fl(fl(k sx) fl(k sx)) and Y, Z alike with
+ * spacing = {sz, sy, sx}: three HOST doubles copied into the kernel arguments; +inf everywhere
+ * when feat has no feature voxel.  Three launches (W, H, D passes), no atomics, every loop
+ * bounded by an axis length.                                                                   */
+int pcms_edt_sq(const unsigned char* feat, const double* spacing, double* out, void* work, int D, int H, int W,
+                hipStream_t s);
+/* One direction of predict.surface_metrics.  sq_b: pcms_edt_sq of b's surface.  sd_sq_out[i] =
+ * sq_b[i] at the voxels of surface(mask_a) (computed here), -1.0 elsewhere.  stats (device, 24
+ * bytes, 8-byte aligned): [0] the number of surface voxels as int64, [1] the maximum of
+ * sd_sq_out as a double (-1.0 without a surface voxel), [2] the sum of sqrt(sd_sq_out) over the
+ * surface voxels as a double: per-workgroup partials in work, folded by one workgroup in a fixed
+ * order, so the sum is the same from run to run.  Two launches.                                */
+int pcms_surface_distance_stats(const unsigned char* mask_a, const double* sq_b, double* sd_sq_out, void* stats,
+                                void* work, int D, int H, int W, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

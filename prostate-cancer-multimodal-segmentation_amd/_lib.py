@@ -127,6 +127,10 @@ SIGNATURES = {
     "pcms_components_work_ints": "iii",
     "pcms_components_label": "piippiiis",
     "pcms_mask_postprocess": "pppiiiiiiis",
+    "pcms_edt_work_bytes": "iii",
+    "pcms_mask_surface": "ppiiis",
+    "pcms_edt_sq": "ppppiiis",  # spacing: a host pointer (ctypes.addressof)
+    "pcms_surface_distance_stats": "pppppiiis",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

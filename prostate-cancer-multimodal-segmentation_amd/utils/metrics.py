@@ -10,8 +10,10 @@ from __future__ import annotations
 import json
 import os
 from datetime import datetime
-from typing import Dict, Iterable, List, Optional
+import math
+from typing import Dict, Iterable, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from ..data import device_batch
@@ -32,10 +34,51 @@ def calculate_iou(pred: torch.Tensor, target: torch.Tensor) -> float:
     return float(inter / (union + 1e-8))
 
 
+def _as_volume(m):
+    """A mask as a (D, H, W) volume: leading dimensions of size 1 (the channel of ``mask[i]`` at
+    the Dice call sites) are squeezed away."""
+    while m.ndim > 3 and m.shape[0] == 1:
+        m = m[0]
+    if m.ndim != 3:
+        raise ValueError(f"a mask is a (D, H, W) volume, optionally behind dimensions of size 1; got {tuple(m.shape)}")
+    return m
+
+
+def calculate_surface_metrics(pred, target, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> Dict:
+    """Boundary metrics of two binary masks (foreground ``!= 0``) in the units of ``spacing =
+    (sz, sy, sx)``: ``hd`` (Hausdorff distance), ``hd95`` (its 95th percentile, MedPy's), ``assd``
+    (average symmetric surface distance), ``n_a`` / ``n_b`` (surface voxels of pred / target).
+    CUDA tensors are scored on the device (predict.surface_metrics_device: exact distance
+    transform in HIP), numpy arrays by the host form (predict.surface_metrics); a CPU tensor
+    raises, as everywhere in pcms_amd.  Both surfaces empty: 0.0; exactly one empty: inf."""
+    from .. import predict
+    if isinstance(pred, np.ndarray) and isinstance(target, np.ndarray):
+        return predict.surface_metrics(_as_volume(pred), _as_volume(target), spacing)
+    if isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor):
+        p, t = ((_as_volume(m) != 0).to(torch.uint8) if m.device.type == "cuda" else m for m in (pred, target))
+        return predict.surface_metrics_device(p, t, spacing)
+    raise TypeError("pred and target are both CUDA tensors or both numpy arrays, got "
+                    f"{type(pred).__name__} and {type(target).__name__}")
+
+
+def calculate_hd95(pred, target, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> float:
+    """The 95th-percentile Hausdorff distance (``calculate_surface_metrics``'s ``hd95``)."""
+    return calculate_surface_metrics(pred, target, spacing)["hd95"]
+
+
+def calculate_assd(pred, target, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> float:
+    """The average symmetric surface distance (``calculate_surface_metrics``'s ``assd``)."""
+    return calculate_surface_metrics(pred, target, spacing)["assd"]
+
+
 @torch.no_grad()
-def evaluate(model, loader: Iterable, threshold: float = 0.5, device=None) -> Dict:
+def evaluate(model, loader: Iterable, threshold: float = 0.5, device=None, surface_metrics: bool = False,
+             spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> Dict:
     """Per-case Dice / IoU of ``model.inference`` masks against binarised labels, and their
-    means (the ModelValidator loop, validate_model.py:226-274, one case per batch item)."""
+    means (the ModelValidator loop, validate_model.py:226-274, one case per batch item).  With
+    ``surface_metrics=True`` every case also carries ``hd95`` / ``assd`` / ``hd`` at ``spacing``
+    (z, y, x; ``calculate_surface_metrics`` on the device) and the result ``mean_hd95`` /
+    ``mean_assd`` over the ``surface_cases`` cases where they are finite."""
     device = device or next(model.parameters()).device
     model.eval()
     cases: List[Dict] = []
@@ -48,16 +91,28 @@ def evaluate(model, loader: Iterable, threshold: float = 0.5, device=None) -> Di
         for i in range(x.shape[0]):
             cases.append({"case_id": ids[i], "dice": calculate_dice_score(mask[i], y[i]),
                           "iou": calculate_iou(mask[i], y[i])})
+            if surface_metrics:
+                m = calculate_surface_metrics(mask[i], y[i], spacing)
+                cases[-1].update(hd95=m["hd95"], assd=m["assd"], hd=m["hd"])
     n = max(len(cases), 1)
-    return {"cases": cases, "mean_dice": sum(c["dice"] for c in cases) / n,
-            "mean_iou": sum(c["iou"] for c in cases) / n}
+    result = {"cases": cases, "mean_dice": sum(c["dice"] for c in cases) / n,
+              "mean_iou": sum(c["iou"] for c in cases) / n}
+    if surface_metrics:
+        finite = [c for c in cases if math.isfinite(c["hd95"]) and math.isfinite(c["assd"])]
+        k = max(len(finite), 1)
+        result.update(mean_hd95=sum(c["hd95"] for c in finite) / k, mean_assd=sum(c["assd"] for c in finite) / k,
+                      surface_cases=len(finite))
+    return result
 
 
 class ModelValidator:
     """script/validate_model.py:98-274: load a checkpoint (either form), run the test loader
     through ``UNet3D.inference`` (HIP eval forward, sigmoid > 0.5 in the head kernel), per-case
     Dice / IoU, and write ``validation_results.json`` to ``config['save_dir']`` with the
-    reference's keys (timestamp, avg_dice, avg_iou, case_count, case_results)."""
+    reference's keys (timestamp, avg_dice, avg_iou, case_count, case_results).  With
+    ``config['surface_metrics']`` (default False) the cases are also scored by ``hd95`` / ``assd``
+    / ``hd`` at ``config['spacing']`` ((z, y, x), default (1, 1, 1)) and the JSON gains
+    ``avg_hd95`` and ``avg_assd``."""
 
     def __init__(self, config: dict, model=None, test_loader: Optional[Iterable] = None):
         from ..models.unet3d import UNet3D, load_weights
@@ -78,9 +133,13 @@ class ModelValidator:
         self.test_loader = test_loader
 
     def validate(self):
-        r = evaluate(self.model, self.test_loader, threshold=0.5, device=self.device)
+        surface = bool(self.config.get("surface_metrics", False))
+        r = evaluate(self.model, self.test_loader, threshold=0.5, device=self.device, surface_metrics=surface,
+                     spacing=tuple(self.config.get("spacing", (1.0, 1.0, 1.0))))
         results = {"timestamp": datetime.now().strftime("%Y-%m-%d %H:%M:%S"), "avg_dice": r["mean_dice"],
                    "avg_iou": r["mean_iou"], "case_count": len(r["cases"]), "case_results": r["cases"]}
+        if surface:
+            results.update(avg_hd95=r["mean_hd95"], avg_assd=r["mean_assd"])
         save_dir = self.config.get("save_dir")
         if save_dir:
             os.makedirs(save_dir, exist_ok=True)
