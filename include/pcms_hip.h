@@ -449,6 +449,28 @@ int pcms_resample_affine_linear(const void* src, int datatype, int Di, int Hi, i
 int pcms_resample_affine_label(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
                                double scl_inter, const double* affine12, float* out, int D, int H, int W,
                                hipStream_t s);
+/* Elastic deformation in the same launch (data.resample_deform on the device, bit for bit).
+ * field: gd * gh * gw * 3 DEVICE doubles, the control grid P[gd][gh][gw][3] of a uniform cubic
+ * B-spline over the output grid's index space, 8-byte aligned; each workgroup copies it into LDS.
+ * For output index i of an axis of extent N with g control points: x = (double)i * ((double)
+ * (g - 3) / (double)N), k = floor(x), s = x - k, r = 1 - s, s2 = s s, s3 = s2 s,
+ * b0 = ((r r) r) / 6, b1 = ((3 s3 - 6 s2) + 4) / 6, b2 = ((((-3 s3) + 3 s2) + 3 s) + 1) / 6,
+ * b3 = s3 / 6, and for component c in (D, H, W)
+ * u_c = sum_jd bd[jd] (sum_jh bh[jh] (sum_jw bw[jw] P[kd + jd][kh + jh][kw + jw][c])), every sum
+ * left to right from j = 0, every product, sum and IEEE division rounded on its own in fp64.
+ * The voxel then samples the source at c_a = ((A[a][0] p_d + A[a][1] p_h) + A[a][2] p_w) + t[a]
+ * with p_a = (double)index_a + u_a, and everything after the coordinate is
+ * pcms_resample_affine_linear's; a zero field gives its result.  The field's values are not
+ * checked (device memory): a non-finite displacement gives a NaN coordinate, which is outside.
+ * Rejects what pcms_resample_affine_linear rejects, a NULL or misaligned field, any of gd / gh /
+ * gw below 4 and gd * gh * gw above 512.                                                    */
+int pcms_resample_deform_linear(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
+                                double scl_inter, const double* affine12, const double* field, int gd, int gh, int gw,
+                                float gain, float bias, float* out, int D, int H, int W, hipStream_t s);
+/* The label form: pcms_resample_affine_label at the deformed position.                      */
+int pcms_resample_deform_label(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope, double scl_inter,
+                               const double* affine12, const double* field, int gd, int gh, int gw, float* out, int D,
+                               int H, int W, hipStream_t s);
 
 /* ---- case prediction: predict.py's host forms on the device (script/predict.py) ------ */
 /* lohi[0] / lohi[1]: the minimum / maximum of the n decoded fp32 values of a volume (decoded

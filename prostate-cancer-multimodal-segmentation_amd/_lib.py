@@ -119,6 +119,8 @@ SIGNATURES = {
     "pcms_resample_label": "piiiiddpiiis",
     "pcms_resample_affine_linear": "piiiiddpffpiiis",  # affine12: a host pointer (ctypes.addressof)
     "pcms_resample_affine_label": "piiiiddppiiis",
+    "pcms_resample_deform_linear": "piiiiddppiiiffpiiis",  # field: a device pointer (fp64 control grid)
+    "pcms_resample_deform_label": "piiiiddppiiipiiis",
     "pcms_volume_minmax_work_floats": "l",
     "pcms_volume_minmax": "pilddpps",
     "pcms_resample_linear_norm": "piiiiddppiiis",

@@ -99,46 +99,13 @@ int resample(bool label, const void* src, int code, int Di, int Hi, int Wi, doub
 }
 
 // ---- training-time augmentation: the same gather under a full 3x4 affine (data.resample_affine) ----
-// Output index (d, h, w) samples the source at c_a = ((A[a][0] d + A[a][1] h) + A[a][2] w) + t[a]
-// (fp64, every product and sum rounded on its own, in this order); with A = diag(n_in / n_out)
-// and t = 0 that is the plain kernels' coordinate.  A coordinate may lie anywhere (or be
-// inf / NaN after an overflow), so inside / outside is decided on the doubles and an index is
-// formed only from a coordinate known to be inside.
-struct Row {
-  double x, y, z, t;
-};
-struct Affine {
-  Row d, h, w;
-};
-struct Dims {
-  int Di, Hi, Wi, D, H, W;
-};
-
-__device__ __forceinline__ double affine_coord(const Row& r, double d, double h, double w) {
-  return ((r.x * d + r.y * h) + r.z * w) + r.t;
-}
-// ITK's buffer rule (data._axis_linear): inside iff -0.5 <= c < n - 0.5; false for NaN
-__device__ __forceinline__ bool linear_inside(double c, int n) { return c >= -0.5 && c < (double)n - 0.5; }
-// neighbours floor(c), floor(c) + 1 of an inside coordinate, each clamped to [0, n - 1] (c may be
-// below 0 here: the lower clamp binds)
-__device__ __forceinline__ Tap affine_tap(double c, int n) {
-  Tap t;
-  const double f = floor(c);
-  const long i0 = (int)f;  // -1 <= f <= n - 1
-  t.w = c - f;
-  t.lo = i0 < 0 ? 0 : i0 > n - 1 ? n - 1 : i0;
-  t.hi = i0 + 1 < 0 ? 0 : i0 + 1 > n - 1 ? n - 1 : i0 + 1;
-  t.outside = false;
-  return t;
-}
-
+// The coordinate, the inside rules and the gather are resample_common.h's (deform.hip shares them).
 template <typename T>
 __global__ void __launch_bounds__(TPB) resample_affine_linear_kernel(const T* __restrict__ src, float* __restrict__ out,
                                                                      Affine m, Dims g, Scale sc, float gain, float bias,
                                                                      int intensity) {
   const long HW = (long)g.H * g.W;
   const long total = (long)g.D * HW;
-  const long sH = g.Wi, sD = (long)g.Hi * g.Wi;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int d = (int)(i / HW);
     const long r = i - d * HW;
@@ -146,33 +113,8 @@ __global__ void __launch_bounds__(TPB) resample_affine_linear_kernel(const T* __
     const double fd = (double)d, fh = (double)h, fw = (double)w;
     const double cd = affine_coord(m.d, fd, fh, fw), ch = affine_coord(m.h, fd, fh, fw),
                  cw = affine_coord(m.w, fd, fh, fw);
-    float res = 0.f;
-    if (linear_inside(cd, g.Di) && linear_inside(ch, g.Hi) && linear_inside(cw, g.Wi)) {
-      const Tap td = affine_tap(cd, g.Di), th = affine_tap(ch, g.Hi), tw = affine_tap(cw, g.Wi);
-      double vh[2];
-#pragma unroll
-      for (int jw = 0; jw < 2; ++jw) {
-        const long xw = jw ? tw.hi : tw.lo;
-        double vd[2];
-#pragma unroll
-        for (int jh = 0; jh < 2; ++jh) {
-          const long xh = (jh ? th.hi : th.lo) * sH + xw;
-          vd[jh] = lerp((double)image_value(src[td.lo * sD + xh], sc), (double)image_value(src[td.hi * sD + xh], sc),
-                        td.w);
-        }
-        vh[jw] = lerp(vd[0], vd[1], th.w);
-      }
-      res = (float)lerp(vh[0], vh[1], tw.w);
-      if (intensity) res = res * gain + bias;  // two fp32 roundings (contraction is off)
-    }
-    out[i] = res;
+    out[i] = affine_linear_value(src, g, sc, cd, ch, cw, gain, bias, intensity);
   }
-}
-
-// nearest index floor(c + 0.5) of one axis; -1: outside [0, n) (also for NaN), the output is 0
-__device__ __forceinline__ long affine_nearest(double c, int n) {
-  const double k = floor(c + 0.5);
-  return (k >= 0.0 && k < (double)n) ? (long)(int)k : -1;
 }
 
 // the label: (float)value > 0 of the nearest voxel, the decoded value rounded to fp32 first
@@ -186,23 +128,8 @@ __global__ void __launch_bounds__(TPB) resample_affine_label_kernel(const T* __r
     const long r = i - d * HW;
     const int h = (int)(r / g.W), w = (int)(r - (long)h * g.W);
     const double fd = (double)d, fh = (double)h, fw = (double)w;
-    const long kd = affine_nearest(affine_coord(m.d, fd, fh, fw), g.Di),
-               kh = affine_nearest(affine_coord(m.h, fd, fh, fw), g.Hi),
-               kw = affine_nearest(affine_coord(m.w, fd, fh, fw), g.Wi);
-    float res = 0.f;
-    if (kd >= 0 && kh >= 0 && kw >= 0) {
-      const T raw = src[(kd * g.Hi + kh) * g.Wi + kw];
-      bool fg;
-      if (sc.on) {
-        fg = (float)scaled(raw, sc) > 0.f;
-      } else if constexpr (sizeof(T) == 8 && std::is_floating_point<T>::value) {
-        fg = (float)raw > 0.f;
-      } else {
-        fg = raw > (T)0;  // every other type keeps its sign through the fp32 rounding
-      }
-      res = fg ? 1.f : 0.f;
-    }
-    out[i] = res;
+    out[i] = affine_label_value(src, g, sc, affine_coord(m.d, fd, fh, fw), affine_coord(m.h, fd, fh, fw),
+                                affine_coord(m.w, fd, fh, fw));
   }
 }
 
@@ -222,14 +149,8 @@ int launch_affine(bool label, const void* src, float* out, const Affine& m, cons
 
 int resample_affine(bool label, const void* src, int code, int Di, int Hi, int Wi, double slope, double inter,
                     const double* a, float gain, float bias, float* out, int D, int H, int W, hipStream_t s) {
-  if (src == nullptr || out == nullptr || a == nullptr) return -1;
-  if (Di < 1 || Hi < 1 || Wi < 1 || D < 1 || H < 1 || W < 1) return -1;
-  if (((uintptr_t)out) % alignof(float) != 0) return -1;
-  for (int i = 0; i < 12; ++i)
-    if (!std::isfinite(a[i])) return -1;
-  if (!std::isfinite(gain) || !std::isfinite(bias)) return -1;
-  // affine12: row-major A[3][3], then t[3]; copied into the kernel arguments
-  const Affine m{Row{a[0], a[1], a[2], a[9]}, Row{a[3], a[4], a[5], a[10]}, Row{a[6], a[7], a[8], a[11]}};
+  if (!affine_args_ok(src, out, a, Di, Hi, Wi, D, H, W, gain, bias)) return -1;
+  const Affine m = make_affine(a);  // copied into the kernel arguments
   const Dims g{Di, Hi, Wi, D, H, W};
   const Scale sc = make_scale(slope, inter);
   return for_datatype(

@@ -1,6 +1,7 @@
-// What the resampling kernels of resample.hip (loader, augmentation) and predict.hip (case
-// prediction) share: the per-axis geometry and the 8-corner gather of data.resample, read_nifti's
-// decoding of a voxel and the dispatch over the NIfTI datatype codes.  Every product and sum must
+// What the resampling kernels of resample.hip (loader, augmentation), deform.hip (elastic
+// augmentation) and predict.hip (case prediction) share: the per-axis geometry and the 8-corner
+// gather of data.resample, the coordinate, inside rules and gather of data.resample_affine,
+// read_nifti's decoding of a voxel and the dispatch over the NIfTI datatype codes.  Every product and sum must
 // round on its own, as numpy's do: no contraction into FMAs from here to the end of the
 // including file.
 #pragma once
@@ -86,6 +87,112 @@ __device__ __forceinline__ float gather_linear(const Axis& ad, const Axis& ah, c
     vh[jw] = ah.ident ? vd[0] : lerp(vd[0], vd[1], th.w);
   }
   return (float)(aw.ident ? vh[0] : lerp(vh[0], vh[1], tw.w));
+}
+
+// ---- the gather under a full 3x4 affine (data.resample_affine; resample.hip and deform.hip) ----
+// Output position (d, h, w) samples the source at c_a = ((A[a][0] d + A[a][1] h) + A[a][2] w) + t[a]
+// (fp64, every product and sum rounded on its own, in this order); with A = diag(n_in / n_out)
+// and t = 0 that is the plain kernels' coordinate.  A coordinate may lie anywhere (or be
+// inf / NaN after an overflow), so inside / outside is decided on the doubles and an index is
+// formed only from a coordinate known to be inside.
+struct Row {
+  double x, y, z, t;
+};
+struct Affine {
+  Row d, h, w;
+};
+struct Dims {
+  int Di, Hi, Wi, D, H, W;
+};
+
+// affine12 (row-major A[3][3], then t[3]) as the kernel argument
+inline Affine make_affine(const double* a) {
+  return Affine{Row{a[0], a[1], a[2], a[9]}, Row{a[3], a[4], a[5], a[10]}, Row{a[6], a[7], a[8], a[11]}};
+}
+
+__device__ __forceinline__ double affine_coord(const Row& r, double d, double h, double w) {
+  return ((r.x * d + r.y * h) + r.z * w) + r.t;
+}
+// ITK's buffer rule (data._axis_linear): inside iff -0.5 <= c < n - 0.5; false for NaN
+__device__ __forceinline__ bool linear_inside(double c, int n) { return c >= -0.5 && c < (double)n - 0.5; }
+// neighbours floor(c), floor(c) + 1 of an inside coordinate, each clamped to [0, n - 1] (c may be
+// below 0 here: the lower clamp binds)
+__device__ __forceinline__ Tap affine_tap(double c, int n) {
+  Tap t;
+  const double f = floor(c);
+  const long i0 = (int)f;  // -1 <= f <= n - 1
+  t.w = c - f;
+  t.lo = i0 < 0 ? 0 : i0 > n - 1 ? n - 1 : i0;
+  t.hi = i0 + 1 < 0 ? 0 : i0 + 1 > n - 1 ? n - 1 : i0 + 1;
+  t.outside = false;
+  return t;
+}
+// nearest index floor(c + 0.5) of one axis; -1: outside [0, n) (also for NaN), the output is 0
+__device__ __forceinline__ long affine_nearest(double c, int n) {
+  const double k = floor(c + 0.5);
+  return (k >= 0.0 && k < (double)n) ? (long)(int)k : -1;
+}
+
+// the linear sample at source coordinates (cd, ch, cw): 0 outside, else the 8 corners lerped
+// over D, then H, then W, one rounding to fp32, then the intensity step
+template <typename T>
+__device__ __forceinline__ float affine_linear_value(const T* __restrict__ src, const Dims& g, const Scale& sc, double cd,
+                                                     double ch, double cw, float gain, float bias, int intensity) {
+  const long sH = g.Wi, sD = (long)g.Hi * g.Wi;
+  float res = 0.f;
+  if (linear_inside(cd, g.Di) && linear_inside(ch, g.Hi) && linear_inside(cw, g.Wi)) {
+    const Tap td = affine_tap(cd, g.Di), th = affine_tap(ch, g.Hi), tw = affine_tap(cw, g.Wi);
+    double vh[2];
+#pragma unroll
+    for (int jw = 0; jw < 2; ++jw) {
+      const long xw = jw ? tw.hi : tw.lo;
+      double vd[2];
+#pragma unroll
+      for (int jh = 0; jh < 2; ++jh) {
+        const long xh = (jh ? th.hi : th.lo) * sH + xw;
+        vd[jh] = lerp((double)image_value(src[td.lo * sD + xh], sc), (double)image_value(src[td.hi * sD + xh], sc),
+                      td.w);
+      }
+      vh[jw] = lerp(vd[0], vd[1], th.w);
+    }
+    res = (float)lerp(vh[0], vh[1], tw.w);
+    if (intensity) res = res * gain + bias;  // two fp32 roundings (contraction is off)
+  }
+  return res;
+}
+
+// the label at source coordinates (cd, ch, cw): (float)value > 0 of the nearest voxel, the decoded
+// value rounded to fp32 first; 0 outside
+template <typename T>
+__device__ __forceinline__ float affine_label_value(const T* __restrict__ src, const Dims& g, const Scale& sc, double cd,
+                                                    double ch, double cw) {
+  const long kd = affine_nearest(cd, g.Di), kh = affine_nearest(ch, g.Hi), kw = affine_nearest(cw, g.Wi);
+  float res = 0.f;
+  if (kd >= 0 && kh >= 0 && kw >= 0) {
+    const T raw = src[(kd * g.Hi + kh) * g.Wi + kw];
+    bool fg;
+    if (sc.on) {
+      fg = (float)scaled(raw, sc) > 0.f;
+    } else if constexpr (sizeof(T) == 8 && std::is_floating_point<T>::value) {
+      fg = (float)raw > 0.f;
+    } else {
+      fg = raw > (T)0;  // every other type keeps its sign through the fp32 rounding
+    }
+    res = fg ? 1.f : 0.f;
+  }
+  return res;
+}
+
+// what every affine entry point checks before a launch (the plain entry points' list, then the
+// matrix and the intensity step)
+inline bool affine_args_ok(const void* src, const float* out, const double* a, int Di, int Hi, int Wi, int D, int H,
+                           int W, float gain, float bias) {
+  if (src == nullptr || out == nullptr || a == nullptr) return false;
+  if (Di < 1 || Hi < 1 || Wi < 1 || D < 1 || H < 1 || W < 1) return false;
+  if (((uintptr_t)out) % alignof(float) != 0) return false;
+  for (int i = 0; i < 12; ++i)
+    if (!std::isfinite(a[i])) return false;
+  return std::isfinite(gain) && std::isfinite(bias);
 }
 
 // f(T{}) for the element type of a NIfTI-1 datatype code (data._NIFTI_DTYPES); -1: no such code

@@ -29,6 +29,9 @@ arithmetic of ``resample`` restated per voxel) into the batch: the same batches 
 3x4 affine per case and epoch (``draw_transform``: flips, rotations, zoom, shift; gain / bias per
 modality) under which every volume of the case is resampled -- ``resample_affine`` on the host,
 pcms_resample_affine_linear / _label in ``assemble_batch`` -- again the same batches bit for bit.
+``Augment.elastic_grid`` / ``elastic_disp`` add a smooth elastic deformation in front of that
+affine: one cubic B-spline control grid per case and epoch, ``resample_deform`` on the host,
+pcms_resample_deform_linear / _label in ``assemble_batch``, the same batches bit for bit too.
 The reference's SimpleITK ``SetSize`` takes (x, y, z), so its non-cubic outputs come out
 axis-reversed; here ``target_size`` is (D, H, W) as documented (:41).
 """
@@ -262,19 +265,28 @@ def resample_affine(vol: np.ndarray, target: Tuple[int, int, int], A, t, nearest
     A = np.asarray(A, dtype=np.float64).reshape(3, 3)
     t = np.asarray(t, dtype=np.float64).reshape(3)
     D, H, W = (int(v) for v in target)
-    n_in = vol.shape
     grid = (np.arange(D, dtype=np.float64).reshape(D, 1, 1), np.arange(H, dtype=np.float64).reshape(1, H, 1),
             np.arange(W, dtype=np.float64).reshape(1, 1, W))
     with np.errstate(over="ignore", invalid="ignore"):  # a far-out coordinate may overflow: it is outside
         c = [((A[a, 0] * grid[0] + A[a, 1] * grid[1]) + A[a, 2] * grid[2]) + t[a] for a in range(3)]
+    return _sample_at(vol, c, nearest, gain, bias)
+
+
+def _sample_at(vol: np.ndarray, c, nearest: bool, gain, bias) -> np.ndarray:
+    """The gather of ``resample_affine`` / ``resample_deform`` at the source coordinates ``c``
+    (three fp64 arrays of the output shape): inside rule, clamps, lerp tree, intensity step and
+    nearest rule as ``resample_affine`` documents them."""
+    n_in = vol.shape
+    shape = c[0].shape
+    with np.errstate(over="ignore", invalid="ignore"):
         if nearest:
             k = [np.floor(c[a] + 0.5) for a in range(3)]
-            inside = np.ones((D, H, W), dtype=bool)
+            inside = np.ones(shape, dtype=bool)
             for a in range(3):
                 inside &= (k[a] >= 0.0) & (k[a] < float(n_in[a]))
             idx = [np.where(inside, k[a], 0.0).astype(np.int64) for a in range(3)]
             return np.where(inside, vol[idx[0], idx[1], idx[2]], 0).astype(np.float32)
-        inside = np.ones((D, H, W), dtype=bool)
+        inside = np.ones(shape, dtype=bool)
         for a in range(3):
             inside &= (c[a] >= -0.5) & (c[a] < n_in[a] - 0.5)
     lo, hi, w = [], [], []
@@ -296,6 +308,84 @@ def resample_affine(vol: np.ndarray, target: Tuple[int, int, int], A, t, nearest
     return np.where(inside, out, np.float32(0.0))
 
 
+MAX_CONTROL_POINTS = 512  # gd * gh * gw of an elastic field: 12 KB of doubles in the kernels' LDS
+
+
+def _bspline_axis(n: int, g: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``(k, b)`` of one output axis of extent ``n`` under ``g`` control points: the first of
+    the four control indices per output index and the (n, 4) uniform cubic B-spline weights,
+    one numpy operation per product, sum and division."""
+    x = np.arange(n, dtype=np.float64) * (float(g - 3) / float(n))
+    f = np.floor(x)
+    s = x - f
+    r = 1.0 - s
+    s2 = s * s
+    s3 = s2 * s
+    b0 = ((r * r) * r) / 6.0
+    b1 = ((3.0 * s3 - 6.0 * s2) + 4.0) / 6.0
+    b2 = ((((-3.0 * s3) + 3.0 * s2) + 3.0 * s) + 1.0) / 6.0
+    b3 = s3 / 6.0
+    return f.astype(np.int64), np.stack([b0, b1, b2, b3], axis=1)
+
+
+def field_displacement(field: np.ndarray, target: Tuple[int, int, int]) -> List[np.ndarray]:
+    """The displacement ``[u_D, u_H, u_W]`` (fp64, output voxels, each of shape ``target``) of
+    a control grid ``field[gd][gh][gw][3]``: the uniform cubic B-spline of ``resample_deform``.
+    The inner sums depend on (control row, control row, w), then (control row, h, w), so they
+    are formed once per such triple -- the same operands in the same order as per voxel."""
+    P = np.asarray(field, dtype=np.float64)
+    if P.ndim != 4 or P.shape[3] != 3 or min(P.shape[:3]) < 4:
+        raise ValueError(f"an elastic field is (gd, gh, gw, 3) with every count >= 4, got {P.shape}")
+    D, H, W = (int(v) for v in target)
+    (kd, bd), (kh, bh), (kw, bw) = (_bspline_axis(n, g) for n, g in zip((D, H, W), P.shape[:3]))
+    u = []
+    with np.errstate(over="ignore", invalid="ignore"):  # a non-finite control vector: NaN, outside
+        for c in range(3):
+            Pc = P[..., c]
+            sw = bw[:, 0] * Pc[:, :, kw]                                  # (gd, gh, W)
+            for j in (1, 2, 3):
+                sw = sw + bw[:, j] * Pc[:, :, kw + j]
+            sh = bh[:, 0, None] * sw[:, kh, :]                            # (gd, H, W)
+            for j in (1, 2, 3):
+                sh = sh + bh[:, j, None] * sw[:, kh + j, :]
+            sd = bd[:, 0, None, None] * sh[kd]                            # (D, H, W)
+            for j in (1, 2, 3):
+                sd = sd + bd[:, j, None, None] * sh[kd + j]
+            u.append(sd)
+    return u
+
+
+def resample_deform(vol: np.ndarray, target: Tuple[int, int, int], A, t, field, nearest: bool = False,
+                    gain: float = 1.0, bias: float = 0.0) -> np.ndarray:
+    """``resample_affine`` with a smooth elastic displacement added to the output index before
+    the affine.  ``field`` is one fp64 control grid ``P[gd][gh][gw][3]`` (every count >= 4), a
+    uniform cubic B-spline over the output grid's index space.  For output index ``i`` of an
+    axis of extent ``N`` with ``g`` control points: ``x = i * ((g - 3) / N)``, ``k = floor(x)``
+    (``0 <= k <= g - 4``), ``s = x - k``, ``r = 1 - s``, ``s2 = s*s``, ``s3 = s2*s`` and
+
+        b0 = ((r*r)*r) / 6                     b1 = ((3*s3 - 6*s2) + 4) / 6
+        b2 = ((((-3*s3) + 3*s2) + 3*s) + 1) / 6        b3 = s3 / 6
+
+    ``u_c = sum_jd bd[jd] * (sum_jh bh[jh] * (sum_jw bw[jw] * P[kd+jd][kh+jh][kw+jw][c]))`` for
+    component c in (D, H, W), every sum left to right from j = 0, every product, sum and
+    division a numpy operation of its own.  The voxel samples the source at
+    ``c_a = ((A[a][0]*p_d + A[a][1]*p_h) + A[a][2]*p_w) + t[a]`` with ``p_a = index_a + u_a``;
+    from there on everything is ``resample_affine``'s, and a zero field gives its result bit
+    for bit.  A non-finite control vector gives NaN coordinates, which are outside (0).
+    libpcms_hip's pcms_resample_deform_linear / _label restate this per voxel and are compared
+    with it on the fp32 bits."""
+    A = np.asarray(A, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    D, H, W = (int(v) for v in target)
+    u = field_displacement(field, (D, H, W))
+    grid = (np.arange(D, dtype=np.float64).reshape(D, 1, 1), np.arange(H, dtype=np.float64).reshape(1, H, 1),
+            np.arange(W, dtype=np.float64).reshape(1, 1, W))
+    with np.errstate(over="ignore", invalid="ignore"):
+        p = [grid[a] + u[a] for a in range(3)]
+        c = [((A[a, 0] * p[0] + A[a, 1] * p[1]) + A[a, 2] * p[2]) + t[a] for a in range(3)]
+    return _sample_at(vol, c, nearest, gain, bias)
+
+
 @dataclasses.dataclass
 class Augment:
     """Training-time augmentation settings (also accepted as a plain dict of these fields).
@@ -307,6 +397,13 @@ class Augment:
     shift_frac: Tuple[float, float, float] = (0.0, 0.0, 0.0)   # max |shift| per axis / output extent
     gain: Tuple[float, float] = (1.0, 1.0)                     # (lo, hi), drawn per modality
     bias: Tuple[float, float] = (0.0, 0.0)                     # (lo, hi), drawn per modality
+    # Elastic deformation (``resample_deform``): control points per output axis (D, H, W), all 0
+    # (off) or each >= 4 with at most MAX_CONTROL_POINTS in all (a scalar: that count on every
+    # axis), and the maximum |control displacement| per axis in output voxels.  Whether the map
+    # stays invertible is the user's concern and is not checked: keep elastic_disp[a] well under
+    # the control spacing N_a / (elastic_grid[a] - 3).
+    elastic_grid: Tuple[int, int, int] = (0, 0, 0)
+    elastic_disp: Tuple[float, float, float] = (0.0, 0.0, 0.0)
 
     @staticmethod
     def of(aug) -> Optional["Augment"]:
@@ -315,7 +412,8 @@ class Augment:
         return Augment(**dict(aug))
 
     def __post_init__(self):
-        for name, n in (("flip_prob", 3), ("rotate_deg", 3), ("shift_frac", 3), ("zoom", 2), ("gain", 2), ("bias", 2)):
+        for name, n in (("flip_prob", 3), ("rotate_deg", 3), ("shift_frac", 3), ("zoom", 2), ("gain", 2), ("bias", 2),
+                        ("elastic_disp", 3)):
             v = getattr(self, name)
             v = (float(v),) * n if np.isscalar(v) and n == 3 else tuple(float(x) for x in v)
             if len(v) != n or not all(np.isfinite(v)):
@@ -323,6 +421,21 @@ class Augment:
             setattr(self, name, v)
         if not self.zoom[0] > 0.0:
             raise ValueError(f"Augment.zoom must be positive, got {self.zoom!r}")
+        if min(self.elastic_disp) < 0.0:
+            raise ValueError(f"Augment.elastic_disp must not be negative, got {self.elastic_disp!r}")
+        g = self.elastic_grid
+        g = (g,) * 3 if np.isscalar(g) else tuple(g)
+        if len(g) != 3 or any(isinstance(v, bool) or int(v) != v for v in g):
+            raise ValueError(f"Augment.elastic_grid must hold 3 integers, got {self.elastic_grid!r}")
+        g = tuple(int(v) for v in g)
+        if any(g) and (min(g) < 4 or g[0] * g[1] * g[2] > MAX_CONTROL_POINTS):
+            raise ValueError("Augment.elastic_grid must be all 0 (off) or hold three counts >= 4 with a product "
+                             f"<= {MAX_CONTROL_POINTS}, got {self.elastic_grid!r}")
+        self.elastic_grid = g
+
+    @property
+    def elastic(self) -> bool:
+        return any(self.elastic_grid)
 
 
 def _matmul3(a: np.ndarray, b: np.ndarray) -> np.ndarray:
@@ -360,11 +473,13 @@ def volume_affine(L, shift, n_in, n_out) -> Tuple[np.ndarray, np.ndarray]:
 class Transform:
     """One case's drawn transform: ``L`` (3x3) and ``shift_frac`` (the shift as a fraction of
     the output extent, per axis) shared by every volume of the case, ``gain`` / ``bias`` per
-    modality."""
+    modality; ``field``: the elastic control grid (fp64 ``(gd, gh, gw, 3)``, output voxels), shared
+    by every volume of the case too, or None."""
     L: np.ndarray
     shift_frac: np.ndarray
     gain: Tuple[float, ...]
     bias: Tuple[float, ...]
+    field: Optional[np.ndarray] = None
 
     def affine(self, n_in, n_out) -> Tuple[np.ndarray, np.ndarray]:
         n_out = tuple(int(v) for v in n_out)
@@ -388,7 +503,10 @@ def draw_transform(aug, seed: int, epoch: int, case_number: int,
       4-6    angles about D, H, W: ``rotate_deg[a] * (2u - 1)`` degrees;
       7      zoom: ``lo + (hi - lo) * u``;
       8-10   shifts of D, H, W: ``shift_frac[a] * (2u - 1)`` of the output extent;
-      then per modality m = 0 .. n_modalities - 1:  gain_m, bias_m: ``lo + (hi - lo) * u`` each."""
+      then per modality m = 0 .. n_modalities - 1:  gain_m, bias_m: ``lo + (hi - lo) * u`` each;
+      then, only with ``elastic_grid`` on, ``gd*gh*gw*3`` more in C order (kd, kh, kw, component):
+      the control displacements ``elastic_disp[c] * (2u - 1)`` (appended, so the draws above are
+      those of the same settings without it)."""
     aug = Augment.of(aug)
     rng = np.random.default_rng([int(seed), int(epoch), int(case_number)])
     flips = [rng.random() < p for p in aug.flip_prob]
@@ -399,12 +517,16 @@ def draw_transform(aug, seed: int, epoch: int, case_number: int,
     for _ in range(int(n_modalities)):
         gain.append(float(aug.gain[0] + (aug.gain[1] - aug.gain[0]) * rng.random()))
         bias.append(float(aug.bias[0] + (aug.bias[1] - aug.bias[0]) * rng.random()))
-    return Transform(compose_transform(flips, angles, zoom), shift, tuple(gain), tuple(bias))
+    field = None
+    if aug.elastic:
+        u = np.array([rng.random() for _ in range(int(np.prod(aug.elastic_grid)) * 3)]).reshape(aug.elastic_grid + (3,))
+        field = np.array(aug.elastic_disp) * (2.0 * u - 1.0) + 0.0
+    return Transform(compose_transform(flips, angles, zoom), shift, tuple(gain), tuple(bias), field)
 
 
 def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool = False,
                     out: Optional[torch.Tensor] = None, affine: Optional[Sequence[float]] = None,
-                    gain: float = 1.0, bias: float = 0.0) -> torch.Tensor:
+                    gain: float = 1.0, bias: float = 0.0, field: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``resample`` of a volume whose bytes are on the GPU, on the current stream: the linear
     form equals ``resample(vol.astype(float32), target)`` bit for bit, ``nearest=True`` gives
     the binarised label ``resample(vol, target, nearest=True) > 0`` as fp32 {0, 1} (for a
@@ -413,7 +535,10 @@ def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool 
     batch) or returns a new one.  There is no CPU form: host bytes raise.
     ``affine`` (twelve doubles, row-major A then t) selects the augmenting entry points:
     ``resample_affine(vol.astype(float32), target, A, t, gain=gain, bias=bias)`` and, with
-    ``nearest``, ``resample_affine(vol, target, A, t, nearest=True) > 0``, bit for bit."""
+    ``nearest``, ``resample_affine(vol, target, A, t, nearest=True) > 0``, bit for bit.
+    ``field`` (a contiguous fp64 ``(gd, gh, gw, 3)`` tensor on the volume's device; needs
+    ``affine``) selects the deforming entry points: ``resample_deform`` with that control grid
+    in place of ``resample_affine``, bit for bit again."""
     from ._lib import call
     target = tuple(int(v) for v in target)
     if raw.data.device.type != "cuda":
@@ -431,12 +556,26 @@ def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool 
           or out.device != raw.data.device):
         raise ValueError(f"out must be a contiguous fp32 {target} tensor on {raw.data.device}")
     if affine is None:
+        if field is not None:
+            raise ValueError("field needs affine: the deformation is applied in front of the affine")
         call("pcms_resample_label" if nearest else "pcms_resample_linear", raw.data, int(raw.code), *raw.shape,
              float(raw.slope), float(raw.inter), out, *target)
         return out
     if len(affine) != 12:
         raise ValueError("affine must hold twelve doubles: row-major A[3][3], then t[3]")
     host = (ctypes.c_double * 12)(*(float(v) for v in affine))  # read during the call (kernel arguments)
+    if field is not None:
+        if (field.dtype != torch.float64 or field.dim() != 4 or field.shape[3] != 3 or not field.is_contiguous()
+                or field.device != raw.data.device):
+            raise ValueError(f"field must be a contiguous fp64 (gd, gh, gw, 3) tensor on {raw.data.device}")
+        grid = tuple(int(v) for v in field.shape[:3])
+        if nearest:
+            call("pcms_resample_deform_label", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
+                 ctypes.addressof(host), field, *grid, out, *target)
+        else:
+            call("pcms_resample_deform_linear", raw.data, int(raw.code), *raw.shape, float(raw.slope),
+                 float(raw.inter), ctypes.addressof(host), field, *grid, float(gain), float(bias), out, *target)
+        return out
     if nearest:
         call("pcms_resample_affine_label", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
              ctypes.addressof(host), out, *target)
@@ -463,7 +602,7 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
                            "pcms_amd has no CPU resampling kernel (use the default loader there)")
     images, labels = raw_batch["raw_images"], raw_batch["raw_label"]
     n, m = len(images), len(images[0])
-    aug = raw_batch.get("augment")  # per case: the drawn (affines, label affine, gains, biases), or absent
+    aug = raw_batch.get("augment")  # per case: the drawn (affines, label affine, gains, biases[, field]), or absent
     with torch.cuda.device(device):
         image = torch.empty((n, m) + target, dtype=torch.float32, device=device)
         label = torch.empty((n, 1) + target, dtype=torch.float32, device=device)
@@ -472,6 +611,9 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
             return raw if raw.data.device.type == "cuda" else raw.pin_memory().to(device, non_blocking=True)
 
         for i in range(n):
+            field = None if aug is None else aug[i].get("field")
+            if field is not None:  # the case's elastic control grid: one upload for its M + 1 launches
+                field = (field if field.device.type == "cuda" else field.pin_memory()).to(device, non_blocking=True)
             for c, raw in enumerate(images[i]):
                 if raw is None:
                     image[i, c].zero_()
@@ -479,9 +621,9 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
                     resample_device(up(raw), target, out=image[i, c])
                 else:
                     resample_device(up(raw), target, out=image[i, c], affine=aug[i]["affine"][c],
-                                    gain=aug[i]["gain"][c], bias=aug[i]["bias"][c])
+                                    gain=aug[i]["gain"][c], bias=aug[i]["bias"][c], field=field)
             resample_device(up(labels[i]), target, nearest=True, out=label[i, 0],
-                            affine=None if aug is None else aug[i]["label_affine"])
+                            affine=None if aug is None else aug[i]["label_affine"], field=field)
     return {"image": image, "label": label, "case_id": list(raw_batch["case_id"])}
 
 
@@ -603,7 +745,8 @@ class ProstateDataset(Dataset):
         """``__getitem__`` under the case's drawn transform: every volume resampled by
         ``resample_affine`` (also one already of the target shape), or -- ``device_resample`` --
         handed over undecoded with the twelve doubles and the gain / bias it is to be resampled
-        with."""
+        with.  With ``elastic_grid`` on the case's control grid goes along: ``resample_deform``
+        here, ``"field"`` in the handed-over dict there."""
         case = self.case_list[idx]
         files = case["modality_files"]
         tf = draw_transform(self.augment, self.augment_seed, self.epoch, idx, len(self.modalities))
@@ -612,7 +755,15 @@ class ProstateDataset(Dataset):
             lab = read_nifti_raw(case["label_path"])
             aug = {"affine": [None if r is None else tf.affine12(r.shape, self.target_size) for r in raws],
                    "label_affine": tf.affine12(lab.shape, self.target_size), "gain": tf.gain, "bias": tf.bias}
+            if self.augment.elastic:  # a CPU tensor, so that the DataLoader's pin_memory handles it
+                aug["field"] = torch.from_numpy(np.ascontiguousarray(tf.field))
             return {"raw_images": raws, "raw_label": lab, "case_id": case["case_id"], "augment": aug}
+        def sample(vol, **kw):  # with an elastic field the same gather at the deformed positions
+            A, t = tf.affine(vol.shape, self.target_size)
+            if tf.field is None:
+                return resample_affine(vol, self.target_size, A, t, **kw)
+            return resample_deform(vol, self.target_size, A, t, tf.field, **kw)
+
         chans = []
         for c, m in enumerate(self.modalities):
             p = files.get(m)
@@ -620,11 +771,9 @@ class ProstateDataset(Dataset):
                 chans.append(np.zeros(self.target_size, dtype=np.float32))
                 continue
             vol = self._first_volume(read_nifti(p)).astype(np.float32)
-            A, t = tf.affine(vol.shape, self.target_size)
-            chans.append(resample_affine(vol, self.target_size, A, t, gain=tf.gain[c], bias=tf.bias[c]))
+            chans.append(sample(vol, gain=tf.gain[c], bias=tf.bias[c]))
         lab = self._first_volume(read_nifti(case["label_path"]))
-        A, t = tf.affine(lab.shape, self.target_size)
-        label = (resample_affine(lab, self.target_size, A, t, nearest=True) > 0).astype(np.float32)[None]
+        label = (sample(lab, nearest=True) > 0).astype(np.float32)[None]
         return {"image": torch.from_numpy(np.stack(chans, 0)).float(), "label": torch.from_numpy(label),
                 "case_id": case["case_id"]}
 
