@@ -554,6 +554,38 @@ int pcms_edt_sq(const unsigned char* feat, const double* spacing, double* out, v
 int pcms_surface_distance_stats(const unsigned char* mask_a, const double* sq_b, double* sd_sq_out, void* stats,
                                 void* work, int D, int H, int W, hipStream_t s);
 
+/* ---- lesion analysis: predict.py's component_table on the device ------------------------- */
+/* labels: a canonical label volume (pcms_components_label's output: 0 on background, 1 + the
+ * smallest flat index of the component elsewhere).  Voxel i is a root iff labels[i] == i + 1; the
+ * row of a component is the number of roots below its own, so rows are in ascending label order.
+ * table: pcms_component_table_bytes(capacity, prob != NULL) bytes of device memory, 8-byte
+ * aligned, columns of `capacity` entries one after the other:
+ *   byte  0 capacity  index_sum  int64 [capacity][3]  sums of d, h, w over the component
+ *   byte 24 capacity  label      int32 [capacity]
+ *   byte 28 capacity  voxels     int32 [capacity]
+ *   byte 32 capacity  bbox       int32 [capacity][6]  dmin, dmax, hmin, hmax, wmin, wmax, inclusive
+ * and with prob (fp32, the labels' shape) three more:
+ *   byte 56 capacity  peak_key   uint64 [capacity]    (key << 32) | ~flat index of the peak voxel
+ *   byte 64 capacity  peak       fp32  [capacity]     the component's maximum of prob
+ *   byte 68 capacity  peak_index int32 [capacity]     the smallest flat index attaining it
+ * The maximum is taken under the total order of key = bits ^ (sign ? 0xFFFFFFFF : 0x80000000):
+ * -0.0 < +0.0 and a positive NaN is above +inf.  Every row of the table is written: a row at or
+ * past the component count holds label 0, voxels 0, sums 0, box minima 2^31 - 1 and maxima -1,
+ * peak_key 0, peak +0.0, peak_index -1.  header (two int32): [0] status, 0 or nonzero where some
+ * label was not canonical (negative, past the volume or not naming a root: that voxel is
+ * skipped, nothing is read or written out of bounds); [1] K, the number of components, also when
+ * K > capacity -- rows at or past capacity are then written nowhere and the caller sizes a
+ * second call from K.  work: pcms_component_table_work_bytes(D, H, W) bytes of device memory,
+ * 4-byte aligned (negative for a dimension < 1 or a volume whose workspace does not fit an int:
+ * about 2^29 voxels).  Integer atomics only, so the bytes are the same from run to run.
+ * Everything is enqueued on s: no allocation, no host synchronisation.  A NULL (but for prob) or
+ * misaligned pointer, a bad dimension, capacity < 1, table / header / work overlapping an input
+ * or one another: negative, no launch, outputs and work untouched.                            */
+int pcms_component_table_work_bytes(int D, int H, int W);
+int pcms_component_table_bytes(int capacity, int with_prob);
+int pcms_component_table(const int* labels, const float* prob, void* table, int capacity, int* header, void* work,
+                         int D, int H, int W, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

@@ -133,6 +133,9 @@ SIGNATURES = {
     "pcms_mask_surface": "ppiiis",
     "pcms_edt_sq": "ppppiiis",  # spacing: a host pointer (ctypes.addressof)
     "pcms_surface_distance_stats": "pppppiiis",
+    "pcms_component_table_work_bytes": "iii",
+    "pcms_component_table_bytes": "ii",
+    "pcms_component_table": "pppippiiis",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

@@ -61,6 +61,23 @@ def calculate_surface_metrics(pred, target, spacing: Sequence[float] = (1.0, 1.0
                     f"{type(pred).__name__} and {type(target).__name__}")
 
 
+def calculate_lesion_metrics(pred, target, spacing: Sequence[float] = (1.0, 1.0, 1.0), connectivity: int = 26,
+                             min_iou: float = 0.1) -> Dict:
+    """Lesion-level detection scores of two binary masks (foreground ``!= 0``): connected
+    components at ``connectivity`` matched one to one at ``min_iou`` (predict.lesion_metrics has
+    the definition and the keys: ``tp`` / ``fp`` / ``fn`` / ``sensitivity`` / ``precision`` / ``f1``
+    and the per-lesion tables).  CUDA tensors are scored on the device
+    (predict.lesion_metrics_device), numpy arrays by the host form; a CPU tensor raises."""
+    from .. import predict
+    if isinstance(pred, np.ndarray) and isinstance(target, np.ndarray):
+        return predict.lesion_metrics(_as_volume(pred), _as_volume(target), None, spacing, connectivity, min_iou)
+    if isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor):
+        p, t = ((_as_volume(m) != 0).to(torch.uint8) if m.device.type == "cuda" else m for m in (pred, target))
+        return predict.lesion_metrics_device(p, t, None, spacing, connectivity, min_iou)
+    raise TypeError("pred and target are both CUDA tensors or both numpy arrays, got "
+                    f"{type(pred).__name__} and {type(target).__name__}")
+
+
 def calculate_hd95(pred, target, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> float:
     """The 95th-percentile Hausdorff distance (``calculate_surface_metrics``'s ``hd95``)."""
     return calculate_surface_metrics(pred, target, spacing)["hd95"]
@@ -73,12 +90,18 @@ def calculate_assd(pred, target, spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> 
 
 @torch.no_grad()
 def evaluate(model, loader: Iterable, threshold: float = 0.5, device=None, surface_metrics: bool = False,
-             spacing: Sequence[float] = (1.0, 1.0, 1.0)) -> Dict:
+             spacing: Sequence[float] = (1.0, 1.0, 1.0), lesion_metrics: bool = False, min_iou: float = 0.1,
+             connectivity: int = 26) -> Dict:
     """Per-case Dice / IoU of ``model.inference`` masks against binarised labels, and their
     means (the ModelValidator loop, validate_model.py:226-274, one case per batch item).  With
     ``surface_metrics=True`` every case also carries ``hd95`` / ``assd`` / ``hd`` at ``spacing``
     (z, y, x; ``calculate_surface_metrics`` on the device) and the result ``mean_hd95`` /
-    ``mean_assd`` over the ``surface_cases`` cases where they are finite."""
+    ``mean_assd`` over the ``surface_cases`` cases where they are finite.  With
+    ``lesion_metrics=True`` every case also carries ``lesion_tp`` / ``lesion_fp`` / ``lesion_fn``
+    (``calculate_lesion_metrics`` at ``connectivity`` and ``min_iou``) and the result their sums
+    over the cases as ``lesion_tp`` / ``lesion_fp`` / ``lesion_fn``, ``lesion_sensitivity`` =
+    tp / (tp + fn), ``lesion_precision`` = tp / (tp + fp), ``lesion_f1`` = 2 tp / (2 tp + fp + fn)
+    (nan where the denominator is 0) and ``mean_fp_per_case``."""
     device = device or next(model.parameters()).device
     model.eval()
     cases: List[Dict] = []
@@ -94,6 +117,9 @@ def evaluate(model, loader: Iterable, threshold: float = 0.5, device=None, surfa
             if surface_metrics:
                 m = calculate_surface_metrics(mask[i], y[i], spacing)
                 cases[-1].update(hd95=m["hd95"], assd=m["assd"], hd=m["hd"])
+            if lesion_metrics:
+                m = calculate_lesion_metrics(mask[i], y[i], spacing, connectivity, min_iou)
+                cases[-1].update(lesion_tp=m["tp"], lesion_fp=m["fp"], lesion_fn=m["fn"])
     n = max(len(cases), 1)
     result = {"cases": cases, "mean_dice": sum(c["dice"] for c in cases) / n,
               "mean_iou": sum(c["iou"] for c in cases) / n}
@@ -102,6 +128,12 @@ def evaluate(model, loader: Iterable, threshold: float = 0.5, device=None, surfa
         k = max(len(finite), 1)
         result.update(mean_hd95=sum(c["hd95"] for c in finite) / k, mean_assd=sum(c["assd"] for c in finite) / k,
                       surface_cases=len(finite))
+    if lesion_metrics:
+        tp, fp, fn = (sum(c[k] for c in cases) for k in ("lesion_tp", "lesion_fp", "lesion_fn"))
+        ratio = lambda num, den: num / den if den else float("nan")  # noqa: E731
+        result.update(lesion_tp=tp, lesion_fp=fp, lesion_fn=fn, lesion_sensitivity=ratio(tp, tp + fn),
+                      lesion_precision=ratio(tp, tp + fp), lesion_f1=ratio(2 * tp, 2 * tp + fp + fn),
+                      mean_fp_per_case=fp / n)
     return result
 
 
