@@ -586,6 +586,41 @@ int pcms_component_table_bytes(int capacity, int with_prob);
 int pcms_component_table(const int* labels, const float* prob, void* table, int capacity, int* header, void* work,
                          int D, int H, int W, hipStream_t s);
 
+/* ---- sliding-window prediction: predict.py's gather_windows / blend_windows on the device ---- */
+/* A window is a wd x wh x ww box of a D x H x W volume (W fastest) at a start (sd, sh, sw): three
+ * int32 of a DEVICE table; it may stick out past the volume.  flipmask: k HOST ints copied into
+ * the kernel arguments, bit 0 / 1 / 2 = the window is mirrored along its D / H / W axis, 1 <= k
+ * <= 8, flipmask[0] == 0, every entry in 0..7.  No window axis is longer than 512 (the blend
+ * keeps the three weight tables in LDS).  Everything is enqueued on s: no allocation, no host
+ * synchronisation, no atomics.  A NULL or misaligned pointer, a size < 1, k outside 1..8,
+ * flipmask[0] != 0 or an entry outside 0..7, a window axis above 512, first_window < 0:
+ * negative, no launch.                                                                        */
+/* predict.gather_windows for the B windows of starts[B][3]: out is (B k, C, wd, wh, ww) fp32, all
+ * of it written; entry i k + j at (c, a, b, e) is x[c] at start_i + (a', b', e'), the primed index
+ * mirrored (n - 1 - index) along the axes of flipmask[j], or 0.f where that lies outside the
+ * volume (a start is not checked: whatever it is, nothing outside x is read).  One thread forms
+ * four consecutive e; with ww % 4 == 0 and out 16-byte aligned it stores them as one vector.
+ * x is (C, D, H, W) fp32 and must not overlap out.  B k C must fit an int.                     */
+int pcms_window_gather(const float* x, int C, int D, int H, int W, const int* starts, int B, const int* flipmask, int k,
+                       int wd, int wh, int ww, float* out, hipStream_t s);
+/* predict.blend_windows for windows first_window .. first_window + B - 1 of the whole table
+ * starts (row = window index); probs is (B k, wd, wh, ww) fp32, the batch's probabilities in
+ * pcms_window_gather's entry order.  wts: wd + wh + ww DEVICE floats, the three per-axis tables
+ * one after the other.  One thread per voxel of the batch's bounding box (found on the device,
+ * clipped to the volume) reads acc and wsum once, visits the batch's windows covering the voxel
+ * in ascending index -- m = (((p_0 + p_1 at the mirrored index) + ...) / (float)k as
+ * pcms_flip_mean forms it (no division for k == 1), wgt = fl(fl(wtd[a] wth[b]) wtw[e]),
+ * acc = fl(acc + fl(wgt m)), wsum = fl(wsum + wgt) -- and writes each once.  The result is the
+ * same bits however the windows are split into batches, as long as the batches are consecutive
+ * index ranges sent in ascending order on one stream.  acc and wsum are D x H x W fp32, zeroed
+ * by the caller before the first batch; nothing may overlap.                                   */
+int pcms_window_blend(const float* probs, const int* starts, int first_window, int B, const int* flipmask, int k,
+                      const float* wts, int wd, int wh, int ww, float* acc, float* wsum, int D, int H, int W,
+                      hipStream_t s);
+/* prob[i] = acc[i] / wsum[i] (correctly rounded fp32 division) for i < n; 16-byte loads and
+ * stores where the three pointers share their offset within 16 bytes.  prob overlaps neither.  */
+int pcms_window_finish(const float* acc, const float* wsum, float* prob, long n, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

@@ -136,6 +136,9 @@ SIGNATURES = {
     "pcms_component_table_work_bytes": "iii",
     "pcms_component_table_bytes": "ii",
     "pcms_component_table": "pppippiiis",
+    "pcms_window_gather": "piiiipipiiiips",  # flipmask: a host pointer (ctypes.addressof)
+    "pcms_window_blend": "ppiipipiiippiiis",
+    "pcms_window_finish": "pppls",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }
