@@ -621,6 +621,48 @@ int pcms_window_blend(const float* probs, const int* starts, int first_window, i
  * stores where the three pointers share their offset within 16 bytes.  prob overlaps neither.  */
 int pcms_window_finish(const float* acc, const float* wsum, float* prob, long n, hipStream_t s);
 
+/* ---- patch training: data.py's pick_origins / resample_patch on the device ------------------ */
+/* A patch is a wd x wh x ww box of a Gd x Gh x Gw grid (W fastest) at an origin: three int32.
+ * Everything is enqueued on s: no allocation, no host synchronisation, no atomics, so the bytes
+ * are the same from run to run.                                                                */
+/* data.pick_origins: label is the grid's n = Gd Gh Gw DEVICE floats, foreground where > 0 (a NaN
+ * is background), T their number.  rank_u: P DEVICE doubles; fallback: P x 3 DEVICE int32.  picks:
+ * 3 P + 1 DEVICE int32, the P origins, then T.  Patch p takes its fallback row, each entry
+ * clamped into [0, max(G_a - w_a, 0)], when rank_u[p] < 0 or T == 0.  Otherwise r = floor(rank_u[p]
+ * (double)T) capped at T - 1 -- the test is !(r < T - 1), so a NaN or a rank of 1 or more gives
+ * T - 1 -- v is the r-th foreground voxel in flat order (d Gh + h) Gw + w, and the origin is
+ * min(max(v_a - w_a / 2, 0), max(G_a - w_a, 0)) per axis (integer division).  Neither table is
+ * trusted: whatever they hold, nothing outside label is read and nothing outside picks written.
+ * Three launches: workgroups count the foreground of chunks of pcms_foreground_pick_chunk()
+ * consecutive voxels (16-byte loads when label is 16-byte aligned), one workgroup scans the counts
+ * exclusively in place, one workgroup per patch finds its chunk by binary search, re-reads it and
+ * locates the voxel by ballots.  work: pcms_foreground_pick_work_ints(n) DEVICE int32 (negative
+ * for n < 1 or n >= 2^31).  P outside 1..64, n != Gd Gh Gw or n >= 2^31, a grid or patch axis
+ * < 1, a NULL or misaligned pointer: negative, no launch.                                       */
+int pcms_foreground_pick_chunk(void);
+int pcms_foreground_pick_work_ints(long n);
+int pcms_foreground_pick(const float* label, long n, int Gd, int Gh, int Gw, int wd, int wh, int ww,
+                         const double* rank_u, const int* fallback, int P, int* picks, int* work, hipStream_t s);
+/* data.resample_patch for the P patches at origins[P][3] (DEVICE int32, e.g. pcms_foreground_pick's
+ * picks), bit for bit: out + p patch_stride (patch_stride counted in floats, >= D H W, so out can
+ * be channel c of a (P, M, D, H, W) batch) is patch p, D x H x W fp32, all of it written.  Patch
+ * index (a, b, e) stands for grid index q = (a, b, e) + origin_p, formed in 64-bit integers; the
+ * voxel is 0.f where any q_a < 0 or q_a >= G_a, else pcms_resample_affine_linear's value at output
+ * index q: c_a = ((A[a][0] q_d + A[a][1] q_h) + A[a][2] q_w) + t[a] and everything after the
+ * coordinate.  An origin is not checked: the zero rule and the inside rule on the doubles mean
+ * nothing outside src is read.  src, datatype, Di .. scl_inter, affine12 (twelve HOST doubles),
+ * gain, bias: as pcms_resample_affine_linear takes them.  lohi: NULL, or two DEVICE floats (e.g.
+ * pcms_volume_minmax's) that select pcms_resample_linear_norm's corner fl32(fl32(v - lo) / den),
+ * den = fl32((double)hi - (double)lo), 0 when den == 0.  One thread forms four consecutive e of a
+ * row and stores 16 bytes when W % 4 == 0 and out and patch_stride are 16-byte aligned, else up
+ * to four scalars.  Rejects what pcms_resample_affine_linear rejects, a grid axis < 1, a NULL or
+ * misaligned origins, a misaligned lohi, P outside 1..64, patch_stride < D H W and D H above
+ * 2^31 - 1: negative, no launch.                                                              */
+int pcms_patch_resample_linear(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
+                               double scl_inter, const double* affine12, const float* lohi, float gain, float bias,
+                               int Gd, int Gh, int Gw, const int* origins, int P, float* out, long patch_stride, int D,
+                               int H, int W, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

@@ -139,6 +139,10 @@ SIGNATURES = {
     "pcms_window_gather": "piiiipipiiiips",  # flipmask: a host pointer (ctypes.addressof)
     "pcms_window_blend": "ppiipipiiippiiis",
     "pcms_window_finish": "pppls",
+    "pcms_foreground_pick_chunk": "",
+    "pcms_foreground_pick_work_ints": "l",
+    "pcms_foreground_pick": "pliiiiiippipps",  # rank_u (fp64), fallback (int32): device pointers
+    "pcms_patch_resample_linear": "piiiiddppffiiipipliiis",  # affine12: host; lohi (or None), origins: device
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

@@ -107,11 +107,7 @@ __global__ void __launch_bounds__(TPB) minmax_finish_kernel(const float* __restr
 }
 
 // ---- the normalised resample and the mask ----------------------------------------------------
-// predict.normalise of one decoded value: den = fl32((double)hi - (double)lo), formed per thread
-__device__ __forceinline__ float normalised(float v, float lo, float den) {
-  return den == 0.f ? 0.f : (v - lo) / den;
-}
-
+// (a corner is resample_common.h's normalised(): patch.hip forms the same one)
 template <typename T>
 __global__ void __launch_bounds__(TPB) resample_linear_norm_kernel(const T* __restrict__ src,
                                                                    const float* __restrict__ lohi,

@@ -1,5 +1,5 @@
 // What the resampling kernels of resample.hip (loader, augmentation), deform.hip (elastic
-// augmentation) and predict.hip (case prediction) share: the per-axis geometry and the 8-corner
+// augmentation), predict.hip (case prediction) and patch.hip (patch training) share: the per-axis geometry and the 8-corner
 // gather of data.resample, the coordinate, inside rules and gather of data.resample_affine,
 // read_nifti's decoding of a voxel and the dispatch over the NIfTI datatype codes.  Every product and sum must
 // round on its own, as numpy's do: no contraction into FMAs from here to the end of the
@@ -134,10 +134,11 @@ __device__ __forceinline__ long affine_nearest(double c, int n) {
 }
 
 // the linear sample at source coordinates (cd, ch, cw): 0 outside, else the 8 corners lerped
-// over D, then H, then W, one rounding to fp32, then the intensity step
-template <typename T>
-__device__ __forceinline__ float affine_linear_value(const T* __restrict__ src, const Dims& g, const Scale& sc, double cd,
-                                                     double ch, double cw, float gain, float bias, int intensity) {
+// over D, then H, then W, one rounding to fp32, then the intensity step; corner(index) is a
+// source voxel as the fp64 value the lerps read
+template <typename Corner>
+__device__ __forceinline__ float affine_linear_gather(const Dims& g, double cd, double ch, double cw, float gain,
+                                                      float bias, int intensity, Corner corner) {
   const long sH = g.Wi, sD = (long)g.Hi * g.Wi;
   float res = 0.f;
   if (linear_inside(cd, g.Di) && linear_inside(ch, g.Hi) && linear_inside(cw, g.Wi)) {
@@ -150,8 +151,7 @@ __device__ __forceinline__ float affine_linear_value(const T* __restrict__ src, 
 #pragma unroll
       for (int jh = 0; jh < 2; ++jh) {
         const long xh = (jh ? th.hi : th.lo) * sH + xw;
-        vd[jh] = lerp((double)image_value(src[td.lo * sD + xh], sc), (double)image_value(src[td.hi * sD + xh], sc),
-                      td.w);
+        vd[jh] = lerp(corner(td.lo * sD + xh), corner(td.hi * sD + xh), td.w);
       }
       vh[jw] = lerp(vd[0], vd[1], th.w);
     }
@@ -159,6 +159,18 @@ __device__ __forceinline__ float affine_linear_value(const T* __restrict__ src, 
     if (intensity) res = res * gain + bias;  // two fp32 roundings (contraction is off)
   }
   return res;
+}
+// ... of a raw volume: the corners as ProstateDataset.__getitem__ decodes them
+template <typename T>
+__device__ __forceinline__ float affine_linear_value(const T* __restrict__ src, const Dims& g, const Scale& sc, double cd,
+                                                     double ch, double cw, float gain, float bias, int intensity) {
+  return affine_linear_gather(g, cd, ch, cw, gain, bias, intensity,
+                              [&](long x) { return (double)image_value(src[x], sc); });
+}
+
+// predict.normalise of one decoded value: den = fl32((double)hi - (double)lo), formed per thread
+__device__ __forceinline__ float normalised(float v, float lo, float den) {
+  return den == 0.f ? 0.f : (v - lo) / den;
 }
 
 // the label at source coordinates (cd, ch, cw): (float)value > 0 of the nearest voxel, the decoded

@@ -32,6 +32,12 @@ pcms_resample_affine_linear / _label in ``assemble_batch`` -- again the same bat
 ``Augment.elastic_grid`` / ``elastic_disp`` add a smooth elastic deformation in front of that
 affine: one cubic B-spline control grid per case and epoch, ``resample_deform`` on the host,
 pcms_resample_deform_linear / _label in ``assemble_batch``, the same batches bit for bit too.
+``patches=...`` (``PatchSampling``; dataset, loader, ``Trainer`` config) turns on patch training
+for a sliding-window predictor: per case and epoch P crops of the window's shape from the case
+grid, a chosen share centred on a lesion voxel -- ``draw_patches`` / ``pick_origins`` /
+``resample_patch`` on the host, pcms_foreground_pick / pcms_patch_resample_linear in
+``assemble_patch_batch``, the origins chosen and consumed on the device; the same batches bit
+for bit once more.
 The reference's SimpleITK ``SetSize`` takes (x, y, z), so its non-cubic outputs come out
 axis-reversed; here ``target_size`` is (D, H, W) as documented (:41).
 """
@@ -524,6 +530,165 @@ def draw_transform(aug, seed: int, epoch: int, case_number: int,
     return Transform(compose_transform(flips, angles, zoom), shift, tuple(gain), tuple(bias), field)
 
 
+# ---- patch training: foreground-biased crops of the window's shape ---------------------------
+MAX_PATCHES = 64        # patches per case: one workgroup of the pick each, one launch per modality
+MAX_PATCH_AXIS = 512    # the label patches come out of pcms_window_gather, which caps a window axis
+
+
+def _axes3(v, what: str) -> Tuple[int, int, int]:
+    try:
+        out = tuple(v)
+    except TypeError:
+        raise ValueError(f"{what} is three integers (d, h, w), got {v!r}") from None
+    if len(out) != 3 or any(isinstance(a, bool) or int(a) != a for a in out):
+        raise ValueError(f"{what} is three integers (d, h, w), got {v!r}")
+    return tuple(int(a) for a in out)
+
+
+@dataclasses.dataclass
+class PatchSampling:
+    """Patch training settings (also accepted as a plain dict of these fields): every case
+    yields ``patches_per_case`` crops of ``patch_size`` -- the window shape of a sliding-window
+    predictor, every axis a multiple of 16 because the network pools four times -- cut from
+    ``grid``, the case grid the windows slide over (``None``: the shape of the case's label
+    file).  A share ``foreground_prob`` of them is centred on a lesion voxel (``draw_patches``,
+    ``pick_origins``).  ``normalise``: every modality is min-max normalised over its whole volume
+    first, as ``predict.prepare_case`` does.  ``seed`` seeds the patch draws."""
+    patch_size: Tuple[int, int, int] = (16, 128, 128)
+    patches_per_case: int = 2
+    foreground_prob: float = 0.5
+    grid: Optional[Tuple[int, int, int]] = None
+    normalise: bool = False
+    seed: int = 0
+
+    @staticmethod
+    def of(patches) -> Optional["PatchSampling"]:
+        if patches is None or isinstance(patches, PatchSampling):
+            return patches
+        return PatchSampling(**dict(patches))
+
+    def __post_init__(self):
+        self.patch_size = _axes3(self.patch_size, "PatchSampling.patch_size")
+        if any(w < 16 or w % 16 or w > MAX_PATCH_AXIS for w in self.patch_size):
+            raise ValueError("PatchSampling.patch_size: every axis is a multiple of 16 (the network pools four "
+                             f"times) up to {MAX_PATCH_AXIS}, got {self.patch_size}")
+        p = self.patches_per_case
+        if isinstance(p, bool) or int(p) != p or not 1 <= int(p) <= MAX_PATCHES:
+            raise ValueError(f"PatchSampling.patches_per_case is an integer in 1..{MAX_PATCHES}, got {p!r}")
+        self.patches_per_case = int(p)
+        self.foreground_prob = float(self.foreground_prob)
+        if not 0.0 <= self.foreground_prob <= 1.0:  # false for NaN
+            raise ValueError(f"PatchSampling.foreground_prob lies in [0, 1], got {self.foreground_prob!r}")
+        if self.grid is not None:
+            self.grid = _axes3(self.grid, "PatchSampling.grid")
+            if min(self.grid) < 1:
+                raise ValueError(f"PatchSampling.grid: every axis is at least 1, got {self.grid}")
+        self.normalise = bool(self.normalise)
+        self.seed = int(self.seed)
+
+
+def _resample_patch(vol: np.ndarray, grid, A, t, origin, patch, gain, bias) -> np.ndarray:
+    A = np.asarray(A, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    grid, patch, origin = _axes3(grid, "grid"), _axes3(patch, "patch"), _axes3(origin, "origin")
+    shapes = ((-1, 1, 1), (1, -1, 1), (1, 1, -1))
+    idx = [(np.arange(w, dtype=np.int64) + o).reshape(s) for w, o, s in zip(patch, origin, shapes)]
+    p = [i.astype(np.float64) for i in idx]
+    with np.errstate(over="ignore", invalid="ignore"):
+        c = [((A[a, 0] * p[0] + A[a, 1] * p[1]) + A[a, 2] * p[2]) + t[a] for a in range(3)]
+    out = _sample_at(vol, c, False, gain, bias)
+    on_grid = np.ones(patch, dtype=bool)
+    for i, g in zip(idx, grid):
+        on_grid = on_grid & ((i >= 0) & (i < g))
+    return np.where(on_grid, out, np.float32(0.0))
+
+
+def resample_patch(vol: np.ndarray, grid, A, t, origin, patch, gain: float = 1.0, bias: float = 0.0,
+                   normalise: bool = False) -> np.ndarray:
+    """One ``patch`` = (wd, wh, ww) crop of ``resample_affine(vol, grid, A, t, gain=gain,
+    bias=bias)`` at ``origin``, bit for bit, formed from the patch's coordinates alone: patch
+    index (d, h, w) stands for grid index ``p = (d, h, w) + origin`` (integers, exact in fp64) and
+    samples the source at ``c_a = ((A[a][0]*p_d + A[a][1]*p_h) + A[a][2]*p_w) + t[a]``; from the
+    coordinate on everything is ``resample_affine``'s (``_sample_at``).  The result is 0 where any
+    ``p_a < 0`` or ``p_a >= grid[a]``: a patch that sticks out of the grid is zero-padded, as
+    ``predict.gather_windows`` pads a window.  ``normalise``: ``vol`` is first replaced by
+    ``predict.normalise(vol)`` (min-max over the whole volume, the corner rule of
+    pcms_resample_linear_norm).  libpcms_hip's pcms_patch_resample_linear restates this per voxel
+    and is compared with it on the fp32 bits."""
+    if normalise:
+        from .predict import normalise as _normalise
+        vol = _normalise(vol)
+    return _resample_patch(vol, grid, A, t, origin, patch, gain, bias)
+
+
+def draw_patches(sampling, seed: int, epoch: int, case_number: int, grid=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The patch draws of case ``case_number`` in ``epoch``: ``(rank_u, fallback)``, P doubles and
+    a (P, 3) int32 array, a function of ``(sampling, seed, epoch, case_number)`` and the grid
+    alone (``grid``: the case grid when ``sampling.grid`` is None -- the label file's shape).
+
+    Stream: ``np.random.default_rng([seed, epoch, case_number, 1])``, a stream of its own, so
+    ``draw_transform``'s draws do not move.  Per patch, in order, five ``rng.random()`` values are
+    always taken: ``u_mode, u_rank, u_d, u_h, u_w``.  A patch is a foreground patch iff
+    ``u_mode < foreground_prob``: its ``rank_u`` is ``u_rank`` (``pick_origins`` turns it into the
+    rank of a lesion voxel), every other patch has ``rank_u = -1.0``.  ``fallback`` is the origin
+    of a uniformly placed patch, ``int(floor(u_a * (max(G_a - w_a, 0) + 1)))`` per axis: what a
+    patch without a rank, or a case without foreground, takes."""
+    sampling = PatchSampling.of(sampling)
+    grid = sampling.grid if sampling.grid is not None else grid
+    if grid is None:
+        raise ValueError("draw_patches needs the case grid: PatchSampling.grid is None and no grid was given")
+    grid = _axes3(grid, "grid")
+    rng = np.random.default_rng([int(seed), int(epoch), int(case_number), 1])
+    P = sampling.patches_per_case
+    rank_u = np.empty(P, dtype=np.float64)
+    fallback = np.empty((P, 3), dtype=np.int32)
+    for i in range(P):
+        u_mode, u_rank = rng.random(), rng.random()
+        u = [rng.random() for _ in range(3)]
+        rank_u[i] = u_rank if u_mode < sampling.foreground_prob else -1.0
+        fallback[i] = [int(np.floor(u[a] * (max(grid[a] - sampling.patch_size[a], 0) + 1))) for a in range(3)]
+    return rank_u, fallback
+
+
+def pick_origins(label_grid: np.ndarray, patch, rank_u, fallback) -> Tuple[np.ndarray, int]:
+    """``(origins, T)``: the (P, 3) int32 origins of P patches on ``label_grid`` (D, H, W) and the
+    number ``T`` of its voxels ``> 0``.  A patch with ``rank_u >= 0`` on a grid with ``T > 0`` is
+    centred on a lesion voxel: ``r = min(T - 1, int(floor(float64(rank_u) * float64(T))))``, the
+    voxel ``v`` is the ``r``-th foreground voxel in flat order ``(d*H + h)*W + w``
+    (``np.flatnonzero``), and ``o_a = min(max(v_a - w_a // 2, 0), max(G_a - w_a, 0))`` -- so the
+    patch contains ``v`` and its label patch is not empty.  Every other patch takes its
+    ``fallback`` row.  The device form (pcms_foreground_pick) reads both tables from memory it does
+    not trust, and this form states the same rule for what ``draw_patches`` never produces: the
+    test for a fallback patch is ``rank_u < 0`` and the cap is ``r = T - 1 unless floor(..) <
+    T - 1``, so a NaN rank or a rank of 1 or more selects the last foreground voxel, and a fallback
+    entry is clamped into ``[0, max(G_a - w_a, 0)]``."""
+    lab = np.asarray(label_grid)
+    if lab.ndim != 3 or 0 in lab.shape:
+        raise ValueError(f"pick_origins takes a non-empty (D, H, W) label grid, got shape {lab.shape}")
+    patch = _axes3(patch, "patch")
+    if min(patch) < 1:
+        raise ValueError(f"a patch axis is at least 1, got {patch}")
+    rank_u = np.asarray(rank_u, dtype=np.float64).reshape(-1)
+    fallback = np.asarray(fallback).reshape(-1, 3).astype(np.int64)
+    if len(rank_u) != len(fallback) or len(rank_u) == 0:
+        raise ValueError(f"rank_u holds P >= 1 doubles and fallback P rows, got {len(rank_u)} and {len(fallback)}")
+    G = lab.shape
+    top = [max(g - w, 0) for g, w in zip(G, patch)]
+    fg = np.flatnonzero(lab.reshape(-1) > 0)
+    T = int(fg.size)
+    origins = np.empty((len(rank_u), 3), dtype=np.int32)
+    for i, u in enumerate(rank_u.tolist()):
+        if u < 0.0 or T == 0:
+            origins[i] = [min(max(int(o), 0), top[a]) for a, o in enumerate(fallback[i])]
+            continue
+        with np.errstate(over="ignore", invalid="ignore"):
+            x = np.floor(np.float64(u) * np.float64(T))
+        r = int(x) if x < T - 1 else T - 1
+        v = np.unravel_index(int(fg[r]), G)
+        origins[i] = [min(max(int(v[a]) - patch[a] // 2, 0), top[a]) for a in range(3)]
+    return origins, T
+
+
 def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool = False,
                     out: Optional[torch.Tensor] = None, affine: Optional[Sequence[float]] = None,
                     gain: float = 1.0, bias: float = 0.0, field: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -595,6 +760,8 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
     batch: each volume's bytes go up from pinned memory in their native type and one resample
     launch writes its channel plane; ``None`` channels (zero_fill) are zeroed.  Everything is
     enqueued on the current stream.  ``target_size`` defaults to the one the loader recorded."""
+    if "patches" in raw_batch:  # a patch-training loader's batch: the grid and the patch shape ride along
+        return assemble_patch_batch(raw_batch, device)
     target = tuple(int(v) for v in (target_size if target_size is not None else raw_batch["target_size"]))
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
@@ -627,6 +794,71 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
     return {"image": image, "label": label, "case_id": list(raw_batch["case_id"])}
 
 
+def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
+    """A patch-training ``device_resample`` batch -> ``{'image': (N*P, M, wd, wh, ww) f32,
+    'label': (N*P, 1, wd, wh, ww) f32, 'case_id': [...], 'picks': (N, 3P + 1) int32}`` on
+    ``device``, equal to the host loader's batch bit for bit.  Per case: the bytes go up once; one
+    pcms_resample_affine_label launch forms the label on the whole grid; pcms_foreground_pick
+    chooses the P origins there (``picks``: the origins, then the foreground count) and nothing
+    brings them back -- pcms_patch_resample_linear reads them from device memory, once per present
+    modality into that channel of the case's P patches (after pcms_volume_minmax with
+    ``normalise``; ``None`` channels are zeroed), and one pcms_window_gather cuts the label
+    patches.  Everything is enqueued on the current stream, with no host synchronisation."""
+    from ._lib import call, query
+    device = torch.device(device if device is not None else "cuda")
+    if device.type != "cuda":
+        raise RuntimeError(f"a device_resample batch can only be assembled on a GPU, not on '{device}': "
+                           "pcms_amd has no CPU resampling kernel (use the default loader there)")
+    images, labels, draws = raw_batch["raw_images"], raw_batch["raw_label"], raw_batch["patches"]
+    patch = tuple(int(v) for v in raw_batch["patch_size"])
+    normalise = bool(raw_batch["normalise"])
+    n, m = len(images), len(images[0])
+    P = int(draws[0]["rank_u"].numel())
+    nwin = patch[0] * patch[1] * patch[2]
+    no_flip = (ctypes.c_int * 1)(0)  # read during the call (kernel arguments)
+    with torch.cuda.device(device):
+        image = torch.empty((n * P, m) + patch, dtype=torch.float32, device=device)
+        label = torch.empty((n * P, 1) + patch, dtype=torch.float32, device=device)
+        picks = torch.empty((n, 3 * P + 1), dtype=torch.int32, device=device)
+        lohi = torch.empty(2, dtype=torch.float32, device=device) if normalise else None
+
+        def up(t):
+            return t if t.device.type == "cuda" else t.pin_memory().to(device, non_blocking=True)
+
+        for i in range(n):
+            d = draws[i]
+            grid = tuple(int(v) for v in d["grid"])
+            cells = grid[0] * grid[1] * grid[2]
+            if int(d["rank_u"].numel()) != P:
+                raise ValueError("every case of a batch holds the same number of patches")
+            lab = labels[i] if labels[i].data.device.type == "cuda" else labels[i].pin_memory().to(device, True)
+            label_grid = resample_device(lab, grid, nearest=True, affine=d["label_affine"])
+            work = torch.empty(query("pcms_foreground_pick_work_ints", cells), dtype=torch.int32, device=device)
+            call("pcms_foreground_pick", label_grid, cells, *grid, *patch, up(d["rank_u"]), up(d["fallback"]), P,
+                 picks[i], work)
+            for c, raw in enumerate(images[i]):
+                first = image[i * P, c]  # patch p of this channel lies p * m * nwin floats further on
+                if raw is None:
+                    image[i * P:(i + 1) * P, c].zero_()
+                    continue
+                raw = raw if raw.data.device.type == "cuda" else raw.pin_memory().to(device, True)
+                cnt = int(np.prod(raw.shape))
+                if raw.data.dtype != torch.uint8 or raw.data.numel() != cnt * np.dtype(_NIFTI_DTYPES[raw.code]).itemsize:
+                    raise ValueError(f"RawVolume holds {raw.data.numel()} bytes, shape {raw.shape} of datatype "
+                                     f"{raw.code} needs {cnt * np.dtype(_NIFTI_DTYPES[raw.code]).itemsize}")
+                if normalise:
+                    mm = torch.empty(query("pcms_volume_minmax_work_floats", cnt), dtype=torch.float32, device=device)
+                    call("pcms_volume_minmax", raw.data, int(raw.code), cnt, float(raw.slope), float(raw.inter), lohi, mm)
+                host = (ctypes.c_double * 12)(*(float(v) for v in d["affine"][c]))  # read during the call
+                call("pcms_patch_resample_linear", raw.data, int(raw.code), *raw.shape, float(raw.slope),
+                     float(raw.inter), ctypes.addressof(host), lohi, float(d["gain"][c]), float(d["bias"][c]), *grid,
+                     picks[i], P, first, m * nwin, *patch)
+            call("pcms_window_gather", label_grid, 1, *grid, picks[i], P, ctypes.addressof(no_flip), 1, *patch,
+                 label[i * P:(i + 1) * P])
+    return {"image": image, "label": label, "case_id": [cid for cid in raw_batch["case_id"] for _ in range(P)],
+            "picks": picks}
+
+
 def device_batch(batch: Dict, device) -> Dict:
     """What every consumer of a loader's batch calls first: a ``device_resample`` batch is
     assembled on ``device`` (``assemble_batch``); any other batch passes through untouched."""
@@ -637,15 +869,29 @@ class _CollateRaw:
     """Collate of ``device_resample`` samples: raw shapes differ between cases and modalities,
     so the descriptors stay in lists (nothing is stacked); the target size rides along."""
 
-    def __init__(self, target_size):
+    def __init__(self, target_size, patches=None):
         self.target_size = tuple(int(v) for v in target_size)
+        self.patches = PatchSampling.of(patches)
 
     def __call__(self, samples: List[Dict]) -> Dict:
         batch = {"raw_images": [s["raw_images"] for s in samples], "raw_label": [s["raw_label"] for s in samples],
                  "case_id": [s["case_id"] for s in samples], "target_size": self.target_size}
         if samples and "augment" in samples[0]:  # an augmenting dataset: each case's drawn transform rides along
             batch["augment"] = [s["augment"] for s in samples]
+        if self.patches is not None:  # a patch-training dataset: each case's affines and patch draws (CPU tensors)
+            batch["patches"] = [s["patches"] for s in samples]
+            batch["patch_size"], batch["normalise"] = self.patches.patch_size, self.patches.normalise
         return batch
+
+
+def _collate_patches(samples: List[Dict]) -> Dict:
+    """Collate of the host loader's patch samples: a sample holds its case's P patches, a batch
+    concatenates them -- ``image`` (N*P, M, wd, wh, ww), ``label`` (N*P, 1, ...), ``case_id``
+    repeated P times, ``picks`` (N, 3P + 1): each case's origins, then its foreground count."""
+    P = samples[0]["image"].shape[0]
+    return {"image": torch.cat([s["image"] for s in samples], 0), "label": torch.cat([s["label"] for s in samples], 0),
+            "case_id": [s["case_id"] for s in samples for _ in range(P)],
+            "picks": torch.stack([s["picks"] for s in samples], 0)}
 
 
 def _find(base: str, case_id: str) -> Optional[str]:
@@ -661,14 +907,24 @@ class ProstateDataset(Dataset):
 
     def __init__(self, data_dir: str, modalities: Optional[List[str]] = None, missing_strategy: str = "zero_fill",
                  target_size: Tuple[int, int, int] = (128, 128, 128), is_training: bool = True,
-                 data_type: str = "BPH", device_resample: bool = False, augment=None, augment_seed: int = 0):
+                 data_type: str = "BPH", device_resample: bool = False, augment=None, augment_seed: int = 0,
+                 patches=None):
         """``augment`` (an ``Augment`` or a dict of its fields; None: off, every sample as
         before): each case is resampled under a transform drawn by ``draw_transform(augment,
         augment_seed, epoch, case index)``, one geometry for all its modalities and its label,
-        gain / bias per modality; ``set_epoch`` moves to the next epoch's draws."""
+        gain / bias per modality; ``set_epoch`` moves to the next epoch's draws.
+        ``patches`` (a ``PatchSampling`` or a dict of its fields; None: off, every sample as
+        before): patch training -- a sample is the case's P crops of the patch shape, cut from
+        the case grid under that transform (the identity draw without ``augment``) at origins
+        drawn by ``draw_patches`` / ``pick_origins``; ``target_size`` is unused, ``set_epoch``
+        moves the patch draws too, and an elastic ``augment`` is not supported with it."""
         if missing_strategy not in ("zero_fill", "skip", "duplicate"):
             raise ValueError(f"unsupported missing-modality strategy: {missing_strategy}")
         self.augment = Augment.of(augment)
+        self.patches = PatchSampling.of(patches)
+        if self.patches is not None and self.augment is not None and self.augment.elastic:
+            raise ValueError("patches and Augment.elastic_grid cannot be combined: the patch resampler has no "
+                             "deforming form")
         self.augment_seed = int(augment_seed)
         self.epoch = 0
         self.data_dir = data_dir
@@ -736,7 +992,8 @@ class ProstateDataset(Dataset):
         raise ValueError(f"unsupported image dimensions: {a.shape}")
 
     def set_epoch(self, epoch: int) -> None:
-        """The epoch whose transforms ``__getitem__`` draws (no effect without ``augment``).
+        """The epoch whose transforms and patch origins ``__getitem__`` draws (no effect without
+        ``augment`` or ``patches``).
         Call it before iterating the loader: its worker processes start per iteration and
         take the value along."""
         self.epoch = int(epoch)
@@ -777,7 +1034,56 @@ class ProstateDataset(Dataset):
         return {"image": torch.from_numpy(np.stack(chans, 0)).float(), "label": torch.from_numpy(label),
                 "case_id": case["case_id"]}
 
+    def _patched(self, idx: int) -> Dict:
+        """``__getitem__`` of a patch-training dataset: the case's P patches.  One transform per
+        case and epoch (``draw_transform``; the identity draw of ``Augment()`` without
+        ``augment``) maps every volume onto the case grid; the label is formed on the whole grid
+        (``resample_affine(..., nearest=True) > 0``), the origins are picked on it, each modality
+        is sampled at the patches' coordinates alone (``resample_patch``) and the label patches
+        are ``predict.gather_windows`` of the grid label.  ``device_resample``: the volumes are
+        handed over undecoded with the twelve doubles per volume and the patch draws as CPU
+        tensors, and ``assemble_patch_batch`` does all of that on the GPU."""
+        case = self.case_list[idx]
+        files = case["modality_files"]
+        ps = self.patches
+        tf = draw_transform(self.augment if self.augment is not None else Augment(), self.augment_seed, self.epoch,
+                            idx, len(self.modalities))
+        if self.device_resample:
+            raws = [read_nifti_raw(files[m]) if m in files else None for m in self.modalities]
+            lab = read_nifti_raw(case["label_path"])
+            grid = ps.grid if ps.grid is not None else tuple(lab.shape)
+            rank_u, fallback = draw_patches(ps, ps.seed, self.epoch, idx, grid)
+            draws = {"affine": [None if r is None else tf.affine12(r.shape, grid) for r in raws],
+                     "label_affine": tf.affine12(lab.shape, grid), "gain": tf.gain, "bias": tf.bias, "grid": grid,
+                     # CPU tensors, so that the DataLoader's pin_memory handles them
+                     "rank_u": torch.from_numpy(rank_u), "fallback": torch.from_numpy(fallback)}
+            return {"raw_images": raws, "raw_label": lab, "case_id": case["case_id"], "patches": draws}
+        from .predict import gather_windows, normalise
+        lab = self._first_volume(read_nifti(case["label_path"]))
+        grid = ps.grid if ps.grid is not None else tuple(lab.shape)
+        rank_u, fallback = draw_patches(ps, ps.seed, self.epoch, idx, grid)
+        label_grid = (resample_affine(lab, grid, *tf.affine(lab.shape, grid), nearest=True) > 0).astype(np.float32)
+        origins, count = pick_origins(label_grid, ps.patch_size, rank_u, fallback)
+        P = ps.patches_per_case
+        image = np.zeros((P, len(self.modalities)) + ps.patch_size, dtype=np.float32)
+        for c, m in enumerate(self.modalities):
+            p = files.get(m)
+            if p is None:  # zero_fill stays zero
+                continue
+            vol = self._first_volume(read_nifti(p)).astype(np.float32)
+            if ps.normalise:  # once per volume, not per patch
+                vol = normalise(vol)
+            A, t = tf.affine(vol.shape, grid)
+            for k in range(P):
+                image[k, c] = _resample_patch(vol, grid, A, t, origins[k], ps.patch_size, tf.gain[c], tf.bias[c])
+        label = gather_windows(label_grid[None], origins, ps.patch_size)
+        picks = np.concatenate([origins.reshape(-1), np.array([count], dtype=np.int32)]).astype(np.int32)
+        return {"image": torch.from_numpy(image), "label": torch.from_numpy(label), "case_id": case["case_id"],
+                "picks": torch.from_numpy(picks)}
+
     def __getitem__(self, idx: int) -> Dict:
+        if self.patches is not None:
+            return self._patched(idx)
         if self.augment is not None:
             return self._augmented(idx)
         case = self.case_list[idx]
@@ -808,7 +1114,7 @@ def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, mod
                    missing_strategy: str = "zero_fill", target_size=(128, 128, 128), num_workers: int = 0,
                    is_training: bool = True, data_type: str = "BPH", indices=None, rank: int = 0,
                    world_size: int = 1, device_resample: bool = False, augment=None,
-                   augment_seed: int = 0) -> DataLoader:
+                   augment_seed: int = 0, patches=None) -> DataLoader:
     """script/data_loader.py:421-466 (pinned host batches; Trainer stages them to the GPU on
     a copy stream one batch ahead).  ``world_size > 1``: each rank iterates its own
     DistributedSampler shard (call ``loader.sampler.set_epoch(epoch)`` every epoch).
@@ -816,11 +1122,20 @@ def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, mod
     same cases in the same order); ``assemble_batch`` resamples them on the GPU.
     ``augment`` / ``augment_seed``: training-time augmentation (``ProstateDataset``); call the
     dataset's ``set_epoch(epoch)`` every epoch (through a ``Subset``: ``loader.dataset.dataset``),
-    ``Trainer.train`` does.  Both kinds of loader give equal batches with it too."""
+    ``Trainer.train`` does.  Both kinds of loader give equal batches with it too.
+    ``patches`` (``PatchSampling``): patch training -- a batch concatenates the P patches of each
+    of its ``batch_size`` cases, ``image`` (batch_size * P, M, wd, wh, ww), ``label``
+    (batch_size * P, 1, ...), ``case_id`` repeated P times, plus ``picks`` (batch_size, 3P + 1):
+    the origins and the foreground count per case; ``target_size`` is unused.  Both kinds of
+    loader give equal batches here too (``assemble_patch_batch``)."""
+    patches = PatchSampling.of(patches)
     ds = ProstateDataset(data_dir, modalities=modalities, missing_strategy=missing_strategy,
                          target_size=target_size, is_training=is_training, data_type=data_type,
-                         device_resample=device_resample, augment=augment, augment_seed=augment_seed)
-    collate = _CollateRaw(target_size) if device_resample else None
+                         device_resample=device_resample, augment=augment, augment_seed=augment_seed,
+                         patches=patches)
+    collate = _CollateRaw(target_size, patches) if device_resample else None
+    if patches is not None and not device_resample:
+        collate = _collate_patches
     if indices is not None:
         ds = torch.utils.data.Subset(ds, indices)
     sampler = None

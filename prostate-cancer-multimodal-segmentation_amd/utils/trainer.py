@@ -25,7 +25,11 @@ loaders hand over the files' undecoded volumes and ``data.assemble_batch`` resam
 the GPU, on the copy stream beside the previous step; same batches bit for bit), ``augment`` /
 ``augment_seed`` (training-time augmentation of the ``data_dir`` training loader, see
 ``data.Augment``: random flips, rotations, zoom, shifts and per-modality gain / bias, drawn per
-case and epoch; validation never augments; both loaders give the same batches), and the step
+case and epoch; validation never augments; both loaders give the same batches), ``patches``
+(patch training, see ``data.PatchSampling``: every case yields P foreground-biased crops of the
+sliding-window predictor's window shape, a step sees ``batch_size * P`` of them; the validation
+loader cuts patches too, without augmentation and at epoch 0, so the same ones every epoch --
+whole-case sliding-window validation is not part of the trainer), and the step
 variants of the other reference trainers:
   ``max_grad_norm``  clip_grad_norm_(max_norm) before Adam (train_bph.py:166,
                      train_bph_cv.py:311 use 1.0): one fused norm pass, the clip coefficient
@@ -117,7 +121,10 @@ class BaseTrainer:
                               device_resample=bool(self.config.get("device_resample", False)),
                               # the training loader only: validation never augments
                               augment=self.config.get("augment") if mode == "train" else None,
-                              augment_seed=int(self.config.get("augment_seed", 0)))
+                              augment_seed=int(self.config.get("augment_seed", 0)),
+                              # both loaders; the validation dataset's epoch is never moved, so with
+                              # augment=None it cuts the same patches every epoch
+                              patches=self.config.get("patches"))
 
     def _broadcast_params(self):
         eng = self.model.engine()
