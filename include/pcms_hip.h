@@ -226,6 +226,12 @@ int pcms_bn_relu_bwd_eval(int dtype, const void* da, const void* y, const float*
  * the one-launch finalize) or more (2048: the two-stage finalize); v <= 0 queries; returns the
  * previous value; set before the workspace queries */
 int pcms_bn_bwd_rows_cap(int v);
+/* Test switch: an extra block cap on every grid-stride launch and every row-count / workspace
+ * query of the streaming kernels (BatchNorm + ReLU, pools, head, loss, Adam, clip, pack / unpack /
+ * add): each uses min(its own cap, v), so a small v makes a test-sized input take the
+ * many-trips-per-thread paths; default INT_MAX (no extra cap, the product); v <= 0 queries;
+ * returns the previous value; set before the workspace queries */
+int pcms_stream_grid_cap(int v);
 int pcms_bn_bwd_rows(int dtype, int C, long nvox);
 /* dy = BN+ReLU backward(da); dgamma/dbeta += ; part: rows*C*2 fp32; coef: 3*C fp32 (the
  * apply coefficients k1, k2, k3 per channel: dy = k1 g + k2 xhat + k3).  dy == NULL: no

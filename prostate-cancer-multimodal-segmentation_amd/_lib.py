@@ -90,6 +90,7 @@ SIGNATURES = {
     "pcms_convt_wgrad_taps": "i",
     "pcms_convt_reduce_fused": "i",
     "pcms_bn_bwd_rows_cap": "i",
+    "pcms_stream_grid_cap": "i",
     "pcms_convt_wgrad": "ippppiiiiiiiiiis",
     "pcms_convt_wgrad_bias_ws_floats": "iiiiiiii",
     "pcms_convt_wgrad_bias": "ippppppiiiiiiiiiis",
@@ -219,7 +220,7 @@ SWITCHES = ("pcms_conv3_big_min_boxes", "pcms_conv3_big_max_wgs", "pcms_conv3_fw
             "pcms_conv3_small_box_mtw2", "pcms_conv3_wgrad_tg_maxbox", "pcms_conv3_wgrad_k16",
             "pcms_conv3_wgrad_x6_dma", "pcms_conv3_wgrad_reduce_fused", "pcms_conv3_b16_nt8",
             "pcms_stem_wgrad_dense", "pcms_convt_fwd_stream", "pcms_convt_wgrad_taps", "pcms_convt_reduce_fused",
-            "pcms_bn_bwd_rows_cap")
+            "pcms_bn_bwd_rows_cap", "pcms_stream_grid_cap")
 
 
 def switches() -> tuple:

@@ -10,13 +10,26 @@
 //   optim.Adam(wd=1e-5, coupled)  utils/trainer.py:113-117
 // Every per-channel statistic is a two-level reduction: fp32 per-block partials written
 // to a [rows][C][2] buffer, combined in fp64 in a fixed order (run-to-run reproducible).
+// Every launch here is grid-stride with a capped grid; pcms_stream_grid_cap (a test switch,
+// host side only) lowers every cap at once so that tests/test_stream_regimes.py reaches the
+// many-trips-per-thread paths at small shapes.
 #include "common.h"
 #include "pcms_hip.h"
 #include <algorithm>
+#include <climits>
 
 namespace {
 
 constexpr int TPB = 256;
+
+// Host side: every grid-stride launch and every row-count / workspace query of this file caps
+// its grid at min(the site's cap, pcms_stream_grid_cap) -- the default (INT_MAX) leaves every
+// site at its own cap; a small value makes a test-sized input take the many-trips-per-thread
+// paths of the kernels below (their unrolled main loops, wraps across samples).
+int g_stream_grid_cap = INT_MAX;
+inline int stream_grid(long work, int per_block, int cap = 8192) {
+  return grid_for(work, per_block, std::min(cap, g_stream_grid_cap));
+}
 
 // ---------------- input: NCDHW fp32 (N, Cin, V) -> NDHWC T (N, V, Cp) ----------------
 template <typename T>
@@ -1556,12 +1569,12 @@ extern "C" {
 
 int pcms_pack_input(int dtype, const float* in, void* out, int N, int Cin, long V, int Cp, hipStream_t s) {
   if (Cp == 8 && Cin <= 8 && V % 4 == 0 && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0) {
-    const int grid = grid_for((long)N * V / 4, TPB, 16 * 256);  // ~one quad per thread: every load in flight at once
+    const int grid = stream_grid((long)N * V / 4, TPB, 16 * 256);  // ~one quad per thread: every load in flight at once
     if (dtype == PCMS_BF16) hipLaunchKernelGGL(pack_input4_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, s, in, (bf16_t*)out, N, Cin, V);
     else hipLaunchKernelGGL(pack_input4_kernel<float>, dim3(grid), dim3(TPB), 0, s, in, (float*)out, N, Cin, V);
     PCMS_CHECK_LAUNCH();
   }
-  const int grid = grid_for((long)N * V, TPB);
+  const int grid = stream_grid((long)N * V, TPB);
   if (dtype == PCMS_BF16) hipLaunchKernelGGL(pack_input_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, s, in, (bf16_t*)out, N, Cin, V, Cp);
   else hipLaunchKernelGGL(pack_input_kernel<float>, dim3(grid), dim3(TPB), 0, s, in, (float*)out, N, Cin, V, Cp);
   PCMS_CHECK_LAUNCH();
@@ -1590,7 +1603,7 @@ int pcms_bn_ws_doubles(int C) { return kRB * C * 2; }
 int pcms_bn_fold(const float* w, const float* b, const float* gamma, const float* beta, const float* rmean,
                  const float* rvar, float eps, int Cout, long K, float* wo, float* bo, hipStream_t s) {
   if (Cout <= 0 || K <= 0) return -1;
-  hipLaunchKernelGGL(bn_fold_kernel, dim3(grid_for(K, 256, 64), Cout), dim3(256), 0, s, w, b, gamma, beta, rmean, rvar,
+  hipLaunchKernelGGL(bn_fold_kernel, dim3(stream_grid(K, 256, 64), Cout), dim3(256), 0, s, w, b, gamma, beta, rmean, rvar,
                      eps, Cout, K, wo, bo);
   PCMS_CHECK_LAUNCH();
 }
@@ -1604,7 +1617,7 @@ int pcms_bn_eval_coeffs(const float* gamma, const float* beta, const float* rmea
 static int ew_grid(int dtype, int C, long nvox) {
   const int VEC = dtype == PCMS_BF16 ? 8 : 4;
   const int VL = TPB / (C / VEC);
-  return grid_for(nvox, VL * 4, 8192);
+  return stream_grid(nvox, VL * 4, 8192);
 }
 
 int pcms_bn_relu(int dtype, const void* y, void* a, const float* scale, const float* shift, int C, long nvox,
@@ -1652,14 +1665,24 @@ int pcms_bn_bwd_rows_cap(int v) {
   return old;
 }
 
+// test switch: an extra cap on every grid and row count of this file (stream_grid above), so
+// that the capped-grid regimes of the streaming kernels are reachable at a small shape;
+// v <= 0 queries, returns the old value; default INT_MAX (no extra cap); set before the
+// workspace queries
+int pcms_stream_grid_cap(int v) {
+  const int old = g_stream_grid_cap;
+  if (v > 0) g_stream_grid_cap = v;
+  return old;
+}
+
 // number of partial rows pcms_bn_relu_bwd_reduce writes (caller sizes `part`)
 int pcms_bn_bwd_rows(int dtype, int C, long nvox) {
   const int VEC = dtype == PCMS_BF16 ? 8 : 4;
   const int VL = TPB / (C / VEC);
   // small (deep) grids: one trip of 4 rows per thread and 4x the blocks (a block's reduction
   // is a chain of memory latencies), as long as the rows stay on the one-launch finalize
-  const int small = grid_for(nvox, VL * 4, 2048);
-  return small <= kSmallRows ? small : grid_for(nvox, VL * 16, g_bn_rows_cap);
+  const int small = stream_grid(nvox, VL * 4, 2048);
+  return small <= kSmallRows ? small : stream_grid(nvox, VL * 16, g_bn_rows_cap);
 }
 
 int pcms_bn_relu_bwd(int dtype, const void* da, const void* y, const float* scale, const float* shift,
@@ -1712,7 +1735,7 @@ int pcms_bn_relu_bwd_finish(int dtype, const void* da, const void* y, const floa
 
 // grid of the cell kernels: a multiple of CV / gcd so every thread keeps one channel group
 static int cell_grid(long total, int CV, int cap) {
-  int g = grid_for(total, TPB, cap);
+  int g = stream_grid(total, TPB, cap);
   const int per = CV / std::__gcd(CV, TPB);  // blocks per period of cv
   return std::max(per, g / per * per);
 }
@@ -1800,7 +1823,7 @@ int pcms_maxpool_fwd(int dtype, const void* a, void* p, int N, int D, int H, int
   if ((long)N * D * H * W * C >= (1L << 31)) return -7;  // 32-bit index math in the kernel
   const int VEC = dtype == PCMS_BF16 ? 8 : 4;
   const long total = (long)N * (D / 2) * (H / 2) * (W / 2) * (C / VEC);
-  const int grid = grid_for(total, TPB);
+  const int grid = stream_grid(total, TPB);
   if (dtype == PCMS_BF16) hipLaunchKernelGGL(maxpool_fwd_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, s, (const bf16_t*)a, (bf16_t*)p, N, D, H, W, C);
   else hipLaunchKernelGGL(maxpool_fwd_kernel<float>, dim3(grid), dim3(TPB), 0, s, (const float*)a, (float*)p, N, D, H, W, C);
   PCMS_CHECK_LAUNCH();
@@ -1811,7 +1834,7 @@ int pcms_maxpool_bwd(int dtype, const void* a, const void* dp, void* da, int N, 
   if ((long)N * D * H * W * C >= (1L << 31)) return -7;  // 32-bit index math in the kernel
   const int VEC = dtype == PCMS_BF16 ? 8 : 4;
   const long total = (long)N * (D / 2) * (H / 2) * (W / 2) * (C / VEC);
-  const int grid = grid_for(total, TPB);
+  const int grid = stream_grid(total, TPB);
   if (dtype == PCMS_BF16) hipLaunchKernelGGL(maxpool_bwd_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, s, (const bf16_t*)a, (const bf16_t*)dp, (bf16_t*)da, N, D, H, W, C);
   else hipLaunchKernelGGL(maxpool_bwd_kernel<float>, dim3(grid), dim3(TPB), 0, s, (const float*)a, (const float*)dp, (float*)da, N, D, H, W, C);
   PCMS_CHECK_LAUNCH();
@@ -1820,7 +1843,7 @@ int pcms_maxpool_bwd(int dtype, const void* a, const void* dp, void* da, int N, 
 static int box_sum_rows(int dtype, int N, int C, int bd, int bh, int bw) {
   const int VEC = dtype == PCMS_BF16 ? 8 : 4;
   const int VL = TPB / (C / VEC);
-  return grid_for((long)N * bd * bh * bw, VL * 8, 1024);
+  return stream_grid((long)N * bd * bh * bw, VL * 8, 1024);
 }
 int pcms_box_channel_sum_ws_floats(int dtype, int N, int C, int bd, int bh, int bw) {
   return box_sum_rows(dtype, N, C, bd, bh, bw) * C;
@@ -1845,7 +1868,7 @@ static int head_fwd_any(int dtype, const void* a, const float* w, const float* b
                         int N, int ncls, int act, float thr, const float* sc, const float* sh, hipStream_t s) {
   if ((long)N * nvox_per_n >= (1L << 31)) return -7;  // 32-bit index math in the kernel
   if (act < 0 || act > 2) return -1;
-  const int grid = grid_for((long)N * nvox_per_n * 8, TPB);
+  const int grid = stream_grid((long)N * nvox_per_n * 8, TPB);
   const bool nt = (long)N * nvox_per_n * 64 * (dtype == PCMS_BF16 ? 2 : 4) >= kNtBytes;
   const bool bn = sc != nullptr;
   int rc;
@@ -1871,7 +1894,7 @@ int pcms_head_bn_fwd(int dtype, const void* y, const float* scale, const float* 
   return head_fwd_any(dtype, y, w, b, out, nvox_per_n, N, ncls, act, thr, scale, shift, s);
 }
 
-static int head_bwd_rows(long nvox) { return grid_for(nvox * 8, TPB, 2048); }
+static int head_bwd_rows(long nvox) { return stream_grid(nvox * 8, TPB, 2048); }
 
 // the head partial rows [grid][ncls][65] -> dw[k][c] += (k, c), db[k] += (k, 64)
 static int head_finish(int grid, float* ws, int ncls, float* dw, float* db, hipStream_t s) {
@@ -1929,7 +1952,7 @@ int pcms_head_bn_bwd(int dtype, const void* y, const float* scale, const float* 
                      invstd, dgamma, dbeta, coef);
   if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   // pass 2: dy of the BatchNorm input (reads y2, dlogits)
-  const int agrid = grid_for(nvox * 8, TPB);
+  const int agrid = stream_grid(nvox * 8, TPB);
   if (dtype == PCMS_BF16)
     launch_head_apply<bf16_t>(nt, agrid, s, y, dlogits, w, scale, shift, mean, invstd, coef, dy, nvox_per_n, N, ncls);
   else
@@ -1944,7 +1967,7 @@ int pcms_head_bn_bwd_eval(int dtype, const void* y, const float* scale, const fl
   if (!y || !scale || !shift || !dlogits || !w || !dy) return -2;
   const long nvox = (long)N * nvox_per_n;
   const bool nt = nvox * 64 * (dtype == PCMS_BF16 ? 2 : 4) >= kNtBytes;
-  const int grid = grid_for(nvox * 8, TPB);
+  const int grid = stream_grid(nvox * 8, TPB);
   int rc;
   if (dtype == PCMS_BF16) rc = launch_head_eval<bf16_t>(nt, grid, s, y, dlogits, w, scale, shift, dy, nvox_per_n, N, ncls);
   else rc = launch_head_eval<float>(nt, grid, s, y, dlogits, w, scale, shift, dy, nvox_per_n, N, ncls);
@@ -1952,7 +1975,7 @@ int pcms_head_bn_bwd_eval(int dtype, const void* y, const float* scale, const fl
   PCMS_CHECK_LAUNCH();
 }
 
-int pcms_loss_rows(long M) { return grid_for(M, TPB * 8, 1024); }
+int pcms_loss_rows(long M) { return stream_grid(M, TPB * 8, 1024); }
 
 // loss (device fp32 scalar) and sums (device fp64[4]); part: rows*4 floats
 int pcms_loss_fwd(const float* x, const float* t, long M, float smooth, float wb, float wd, float* part,
@@ -1967,7 +1990,7 @@ int pcms_loss_fwd(const float* x, const float* t, long M, float smooth, float wb
 
 int pcms_loss_bwd(const float* x, const float* t, long M, const double* sums, float smooth, float wb, float wd,
                   const float* gout, float* dx, hipStream_t s) {
-  hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid_for(M, TPB)), dim3(TPB), 0, s, x, t, M, sums, smooth, wb, wd, gout, dx);
+  hipLaunchKernelGGL(loss_bwd_kernel, dim3(stream_grid(M, TPB)), dim3(TPB), 0, s, x, t, M, sums, smooth, wb, wd, gout, dx);
   PCMS_CHECK_LAUNCH();
 }
 
@@ -1975,7 +1998,7 @@ int pcms_loss_bwd(const float* x, const float* t, long M, const double* sums, fl
 int pcms_adam(float* p, float* g, float* m, float* v, long n, float step_size, float b1, float b2, float eps,
               float wd, float bc2_sqrt, float gscale, const float* gmul, hipStream_t s) {
   const AdamCoef c{step_size, b1, b2, eps, wd, bc2_sqrt, gscale};
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n, TPB, 16384)), dim3(TPB), 0, s, p, g, m, v, n, c, gmul);
+  hipLaunchKernelGGL(adam_kernel, dim3(stream_grid(n, TPB, 16384)), dim3(TPB), 0, s, p, g, m, v, n, c, gmul);
   PCMS_CHECK_LAUNCH();
 }
 
@@ -1984,14 +2007,14 @@ int pcms_adam_ranges(float* p, float* g, float* m, float* v, const long long* ra
                      const float* gmul, hipStream_t s) {
   if (nranges <= 0) return 0;
   const AdamCoef c{step_size, b1, b2, eps, wd, bc2_sqrt, gscale};
-  hipLaunchKernelGGL(adam_ranges_kernel, dim3(grid_for(max_len, TPB, 2048), nranges), dim3(TPB), 0, s, p, g, m, v,
+  hipLaunchKernelGGL(adam_ranges_kernel, dim3(stream_grid(max_len, TPB, 2048), nranges), dim3(TPB), 0, s, p, g, m, v,
                      ranges, c, gmul);
   PCMS_CHECK_LAUNCH();
 }
 
 int pcms_fill_ranges(float* p, const long long* ranges, int nranges, long max_len, float v, hipStream_t s) {
   if (nranges <= 0) return 0;
-  hipLaunchKernelGGL(fill_ranges_kernel, dim3(grid_for(max_len, TPB, 1024), nranges), dim3(TPB), 0, s, p, ranges, v);
+  hipLaunchKernelGGL(fill_ranges_kernel, dim3(stream_grid(max_len, TPB, 1024), nranges), dim3(TPB), 0, s, p, ranges, v);
   PCMS_CHECK_LAUNCH();
 }
 
@@ -2000,7 +2023,7 @@ int pcms_grad_clip_ws_doubles(void) { return kNormBlocks; }
 int pcms_grad_clip(float* g, long n, float gscale, float max_norm, int apply, double* ws, float* norm_out,
                    float* mul_out, hipStream_t s) {
   if (ws == nullptr || mul_out == nullptr || ((uintptr_t)g & 15)) return -1;
-  const int rows = grid_for(n / 4 + 1, TPB, kNormBlocks);
+  const int rows = stream_grid(n / 4 + 1, TPB, kNormBlocks);
   hipLaunchKernelGGL(sumsq_kernel, dim3(rows), dim3(TPB), 0, s, (const float*)g, n, ws);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
@@ -2008,7 +2031,7 @@ int pcms_grad_clip(float* g, long n, float gscale, float max_norm, int apply, do
                      norm_out, mul_out);
   e = hipGetLastError();
   if (e != hipSuccess || !apply) return (int)e;
-  hipLaunchKernelGGL(scale_kernel, dim3(grid_for(n, TPB, 16384)), dim3(TPB), 0, s, g, n, (const float*)mul_out);
+  hipLaunchKernelGGL(scale_kernel, dim3(stream_grid(n, TPB, 16384)), dim3(TPB), 0, s, g, n, (const float*)mul_out);
   PCMS_CHECK_LAUNCH();
 }
 
@@ -2028,7 +2051,7 @@ int pcms_split_epilogue(int dtype, const float* acc, int splits, const float* bi
 
 int pcms_unpack_output(int dtype, const void* in, float* out, int N, int C, int Cs, long V, hipStream_t s) {
   if (C > Cs) return -1;
-  const int grid = grid_for((long)N * C * V, TPB);
+  const int grid = stream_grid((long)N * C * V, TPB);
   if (dtype == PCMS_BF16) hipLaunchKernelGGL(unpack_output_kernel<bf16_t>, dim3(grid), dim3(TPB), 0, s, (const bf16_t*)in, out, N, C, Cs, V);
   else hipLaunchKernelGGL(unpack_output_kernel<float>, dim3(grid), dim3(TPB), 0, s, (const float*)in, out, N, C, Cs, V);
   PCMS_CHECK_LAUNCH();
@@ -2038,8 +2061,8 @@ int pcms_add(int dtype, void* dst, const void* src, long n, hipStream_t s) {
   const int VEC = dtype == PCMS_BF16 ? 8 : 4;
   if (n % VEC) return -1;
   const long nvec = n / VEC;
-  if (dtype == PCMS_BF16) hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(grid_for(nvec, TPB)), dim3(TPB), 0, s, (bf16_t*)dst, (const bf16_t*)src, nvec);
-  else hipLaunchKernelGGL(add_kernel<float>, dim3(grid_for(nvec, TPB)), dim3(TPB), 0, s, (float*)dst, (const float*)src, nvec);
+  if (dtype == PCMS_BF16) hipLaunchKernelGGL(add_kernel<bf16_t>, dim3(stream_grid(nvec, TPB)), dim3(TPB), 0, s, (bf16_t*)dst, (const bf16_t*)src, nvec);
+  else hipLaunchKernelGGL(add_kernel<float>, dim3(stream_grid(nvec, TPB)), dim3(TPB), 0, s, (float*)dst, (const float*)src, nvec);
   PCMS_CHECK_LAUNCH();
 }
 

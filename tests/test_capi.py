@@ -54,3 +54,26 @@ def test_host_queries_without_gpu():
     assert _lib.query("pcms_conv3_pack_elems", _lib.F32X3, 64, 5) == 1 * 27 * 64 * 16
     assert _lib.query("pcms_conv3_mblocks", 2, 128, 128, 64) == 2 * 16 * 16 * 8
     assert _lib.query("pcms_loss_rows", 1 << 20) > 0
+
+
+def test_stream_grid_cap_switch_caps_the_row_queries():
+    """pcms_stream_grid_cap: v > 0 sets, v <= 0 queries, the old value is returned; the default
+    leaves every row count at its own cap; it is part of the engine's allocation key."""
+    assert "pcms_stream_grid_cap" in _lib.SWITCHES
+    big = _lib.query("pcms_stream_grid_cap", -1)
+    assert big >= 2 ** 30 and _lib.query("pcms_stream_grid_cap", 0) == big
+    before = (_lib.query("pcms_loss_rows", 1 << 24), _lib.query("pcms_bn_bwd_rows", _lib.BF16, 64, 1 << 22),
+              _lib.query("pcms_head_bn_bwd_rows", 1 << 20, 2))
+    assert before == (1024, 512, 2048)
+    try:
+        assert _lib.query("pcms_stream_grid_cap", 3) == big
+        assert _lib.query("pcms_stream_grid_cap", -1) == 3 and 3 in _lib.switches()
+        assert (_lib.query("pcms_loss_rows", 1 << 24), _lib.query("pcms_bn_bwd_rows", _lib.BF16, 64, 1 << 22),
+                _lib.query("pcms_head_bn_bwd_rows", 1 << 20, 2)) == (3, 3, 3)
+        assert _lib.query("pcms_maxpool_bwd_bn_rows", _lib.F32, 2, 32, 32, 32, 64) == 3
+        assert _lib.query("pcms_head_bwd_ws_floats", 1 << 20, 2, 2) == 4 * 2 * 65
+        assert _lib.query("pcms_box_channel_sum_ws_floats", _lib.F32, 2, 64, 32, 32, 32) == 3 * 64
+    finally:
+        assert _lib.query("pcms_stream_grid_cap", big) == 3
+    assert (_lib.query("pcms_loss_rows", 1 << 24), _lib.query("pcms_bn_bwd_rows", _lib.BF16, 64, 1 << 22),
+            _lib.query("pcms_head_bn_bwd_rows", 1 << 20, 2)) == before

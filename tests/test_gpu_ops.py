@@ -775,9 +775,13 @@ def test_convt_fwd_stream(Sin, Sout):
 @pytest.mark.parametrize("dt,code,tol", DTS)
 @pytest.mark.parametrize("ncls", [1, 2])
 def test_head(dt, code, tol, ncls):
-    L = _lib()
+    head_case(_lib(), dt, code, tol, ncls, 2, (5, 6, 7))
+
+
+def head_case(L, dt, code, tol, ncls, N, S):
+    """pcms_head_fwd (logits / sigmoid / mask) and pcms_head_bwd vs fp64 autograd of the 1x1x1
+    conv (also run by tests/test_stream_regimes.py at other shapes and class counts)."""
     g = torch.Generator().manual_seed(1)
-    N, S = 2, (5, 6, 7)
     a = torch.relu(torch.randn(N, 64, *S, generator=g)).to(dt)
     w = torch.randn(ncls, 64, 1, 1, 1, generator=g) * 0.1
     b = torch.randn(ncls, generator=g)

@@ -46,6 +46,12 @@ def _opt(m, name):
 # the same bars against the reference as the plain one
 @pytest.mark.parametrize("name,ckpt", [(n, False) for n in gu.CASES] + [("cfg1_dice", True), ("odd_bcedice", True)])
 def test_fp32_parity_full_step(name, ckpt):
+    fp32_parity_full_step(name, ckpt)
+
+
+def fp32_parity_full_step(name, ckpt):
+    """The body of test_fp32_parity_full_step (also run by tests/test_stream_regimes.py with the
+    streaming kernels' grids capped)."""
     g = gu.load(name)
     m = _build(name, "fp32", ckpt)
     assert gu.sd_hash({k: v.cpu() for k, v in m.state_dict().items()}) == str(g["sd_sha256"])
@@ -138,6 +144,12 @@ def test_fp32_parity_full_step(name, ckpt):
 @pytest.mark.parametrize("name,ckpt", [("c16_bcedice", False), ("cfg1_dice", False), ("odd_bcedice", False),
                                        ("cfg1_dice", True), ("zf_bcedice", False)])
 def test_bf16_parity_step(name, ckpt):
+    bf16_parity_step(name, ckpt)
+
+
+def bf16_parity_step(name, ckpt):
+    """The body of test_bf16_parity_step (also run by tests/test_stream_regimes.py with the
+    streaming kernels' grids capped)."""
     g = gu.load(name)
     m = _build(name, "bf16", ckpt)
     crit, opt = _crit(name), _opt(m, name)
