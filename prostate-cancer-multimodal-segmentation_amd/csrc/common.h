@@ -256,7 +256,23 @@ __device__ __forceinline__ float sum_rows16(const float* src, long step, int n) 
   return sum;
 }
 
+// the tail of an entry point: its last launch's error code is the result
 #define PCMS_CHECK_LAUNCH() return (int)hipGetLastError()
+// a launch that another launch follows: a nonzero launch error returns from the enclosing function
+#define PCMS_LAUNCH(kernel, grid, block, lds, stream, ...)              \
+  do {                                                                  \
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);  \
+    const int rc_ = (int)hipGetLastError();                             \
+    if (rc_ != 0) return rc_;                                           \
+  } while (0)
+
+// host-side pointer checks of the entry points: p not a multiple of a bytes; [a, a + na) and
+// [b, b + nb) (bytes) share a byte
+static inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p) % a != 0; }
+static inline bool overlap(const void* a, long na, const void* b, long nb) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // blocks of a grid-stride launch: one per per_block units of work, between 1 and cap

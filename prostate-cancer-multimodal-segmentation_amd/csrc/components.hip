@@ -237,7 +237,6 @@ __global__ void __launch_bounds__(TPB) cc_fill_kernel(const int* __restrict__ pa
   }
 }
 
-inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p) % a != 0; }
 inline long voxels(int D, int H, int W) {
   if (D < 1 || H < 1 || W < 1) return -1;
   const long n = (long)D * H * W;
@@ -247,20 +246,13 @@ inline u64* winners(int* work) {  // the 8-byte-aligned keys inside the header
   return reinterpret_cast<u64*>((reinterpret_cast<uintptr_t>(work + 2) + 7) & ~(uintptr_t)7);
 }
 
-#define CC_LAUNCH(...)                                  \
-  do {                                                  \
-    hipLaunchKernelGGL(__VA_ARGS__);                    \
-    const int rc_ = (int)hipGetLastError();             \
-    if (rc_ != 0) return rc_;                           \
-  } while (0)
-
 // tile + merge: par holds a forest whose roots are the components' minimum indices
 int label_forest(const uint8_t* mask, int invert, int nfwd, int* par, int* aux, int* work, int D, int H, int W,
                  hipStream_t s) {
   const Tiles tiles{cdiv(H, TH), cdiv(W, TW)};
   const int ntiles = cdiv(D, TD) * tiles.nh * tiles.nw;
-  CC_LAUNCH(cc_tile_kernel, dim3(ntiles), dim3(TPB), 0, s, mask, invert, nfwd, par, aux, work, D, H, W, tiles);
-  if (ntiles > 1) CC_LAUNCH(cc_merge_kernel, dim3(ntiles), dim3(TPB), 0, s, par, nfwd, work, D, H, W, tiles);
+  PCMS_LAUNCH(cc_tile_kernel, dim3(ntiles), dim3(TPB), 0, s, mask, invert, nfwd, par, aux, work, D, H, W, tiles);
+  if (ntiles > 1) PCMS_LAUNCH(cc_merge_kernel, dim3(ntiles), dim3(TPB), 0, s, par, nfwd, work, D, H, W, tiles);
   return 0;
 }
 
@@ -280,7 +272,7 @@ int pcms_components_label(const unsigned char* mask, int invert, int connectivit
   if (mask == nullptr || labels == nullptr || work == nullptr || n < 0 || nfwd == 0) return -1;
   if (misaligned(labels, alignof(int)) || misaligned(work, alignof(int))) return -1;
   int* par = work + HDR;
-  CC_LAUNCH(cc_init_kernel, dim3(1), dim3(TPB), 0, s, work);
+  PCMS_LAUNCH(cc_init_kernel, dim3(1), dim3(TPB), 0, s, work);
   const int rc = label_forest(mask, invert, nfwd, par, nullptr, work, D, H, W, s);
   if (rc != 0) return rc;
   hipLaunchKernelGGL(cc_flatten_kernel<MODE_LABELS>, dim3(grid_for(n, TPB)), dim3(TPB), 0, s, par, labels, work, D, H,
@@ -294,30 +286,30 @@ int pcms_mask_postprocess(const unsigned char* mask, unsigned char* out, int* wo
   const int nfwd = fwd_count(connectivity);
   if (mask == nullptr || out == nullptr || work == nullptr || n < 0 || nfwd == 0) return -1;
   if (misaligned(work, alignof(int)) || keep_largest < 0 || keep_largest > MAX_KEEP || min_voxels < 0) return -1;
-  if (mask < out + n && out < mask + n) return -1;  // out may not alias mask
+  if (overlap(mask, n, out, n)) return -1;  // out may not alias mask
   int* par = work + HDR;
   int* aux = par + n;
   u64* win = winners(work);
   const int grid = grid_for(n, TPB);
-  CC_LAUNCH(cc_init_kernel, dim3(1), dim3(TPB), 0, s, work);
+  PCMS_LAUNCH(cc_init_kernel, dim3(1), dim3(TPB), 0, s, work);
   if (keep_largest == 0 && min_voxels <= 1) {
-    CC_LAUNCH(cc_binarise_kernel, dim3(grid), dim3(TPB), 0, s, mask, out, (int)n);
+    PCMS_LAUNCH(cc_binarise_kernel, dim3(grid), dim3(TPB), 0, s, mask, out, (int)n);
   } else {
     const int rc = label_forest(mask, 0, nfwd, par, aux, work, D, H, W, s);
     if (rc != 0) return rc;
-    CC_LAUNCH(cc_flatten_kernel<MODE_SIZES>, dim3(grid), dim3(TPB), 0, s, par, aux, work, D, H, W);
+    PCMS_LAUNCH(cc_flatten_kernel<MODE_SIZES>, dim3(grid), dim3(TPB), 0, s, par, aux, work, D, H, W);
     for (int k = 0; k < keep_largest; ++k)
-      CC_LAUNCH(cc_topk_kernel, dim3(grid_for(n, TPB * 4)), dim3(TPB), 0, s, (const int*)par, (const int*)aux,
-                win, k, (int)n);
-    CC_LAUNCH(cc_keep_kernel, dim3(grid), dim3(TPB), 0, s, (const int*)par, (const int*)aux, (const u64*)win,
-              keep_largest, min_voxels, out, (int)n);
+      PCMS_LAUNCH(cc_topk_kernel, dim3(grid_for(n, TPB * 4)), dim3(TPB), 0, s, (const int*)par, (const int*)aux,
+                  win, k, (int)n);
+    PCMS_LAUNCH(cc_keep_kernel, dim3(grid), dim3(TPB), 0, s, (const int*)par, (const int*)aux, (const u64*)win,
+                keep_largest, min_voxels, out, (int)n);
   }
   if (fill_holes) {
     // the background of out at 6-connectivity (the dual of 26); its components off every face are holes
     const int rc = label_forest(out, 1, fwd_count(6), par, aux, work, D, H, W, s);
     if (rc != 0) return rc;
-    CC_LAUNCH(cc_flatten_kernel<MODE_FACES>, dim3(grid), dim3(TPB), 0, s, par, aux, work, D, H, W);
-    CC_LAUNCH(cc_fill_kernel, dim3(grid), dim3(TPB), 0, s, (const int*)par, (const int*)aux, out, (int)n);
+    PCMS_LAUNCH(cc_flatten_kernel<MODE_FACES>, dim3(grid), dim3(TPB), 0, s, par, aux, work, D, H, W);
+    PCMS_LAUNCH(cc_fill_kernel, dim3(grid), dim3(TPB), 0, s, (const int*)par, (const int*)aux, out, (int)n);
   }
   return 0;
 }

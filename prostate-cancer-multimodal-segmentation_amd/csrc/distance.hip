@@ -233,11 +233,6 @@ __global__ void __launch_bounds__(TPB) sd_finish_kernel(const double* __restrict
 }
 
 // ---- host side -------------------------------------------------------------------------------
-inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p) % a != 0; }
-inline bool overlap(const void* a, long abytes, const void* b, long bbytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + (uintptr_t)bbytes && y < x + (uintptr_t)abytes;
-}
 inline long voxels(int D, int H, int W) {
   if (D < 1 || H < 1 || W < 1 || D > MAX_AXIS || H > MAX_AXIS || W > MAX_AXIS) return -1;
   const long n = (long)D * H * W;

@@ -244,11 +244,6 @@ __global__ void __launch_bounds__(TPB) lt_decode_kernel(Table t, int capacity) {
   t.peak_index[r] = index;
 }
 
-inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p) % a != 0; }
-inline bool overlap(const void* a, long na, const void* b, long nb) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
 // voxels, or -1 for a bad dimension or a workspace whose bytes do not fit an int
 inline long voxels(int D, int H, int W) {
   if (D < 1 || H < 1 || W < 1) return -1;
@@ -256,13 +251,6 @@ inline long voxels(int D, int H, int W) {
   if (n > (1l << 30)) return -1;
   return 4 * (n + cdiv(n, CHUNK)) > 0x7fffffffl ? -1 : n;
 }
-
-#define LT_LAUNCH(...)                      \
-  do {                                      \
-    hipLaunchKernelGGL(__VA_ARGS__);        \
-    const int rc_ = (int)hipGetLastError(); \
-    if (rc_ != 0) return rc_;               \
-  } while (0)
 
 }  // namespace
 
@@ -299,18 +287,18 @@ int pcms_component_table(const int* labels, const float* prob, void* table, int 
   int* offsets = rank + n;
   const Table t = table_columns(table, capacity);
   const int rows = cdiv(capacity, TPB);
-  LT_LAUNCH(lt_init_kernel, dim3(rows), dim3(TPB), 0, s, t, capacity, with_prob, header);
-  LT_LAUNCH(lt_count_kernel, dim3(nchunks), dim3(TPB), 0, s, labels, offsets, (int)n);
-  LT_LAUNCH(lt_scan_kernel, dim3(1), dim3(TPB), 0, s, offsets, nchunks, header);
-  LT_LAUNCH(lt_scatter_kernel, dim3(nchunks), dim3(TPB), 0, s, labels, (const int*)offsets, rank, t.label, capacity,
-            (int)n);
+  PCMS_LAUNCH(lt_init_kernel, dim3(rows), dim3(TPB), 0, s, t, capacity, with_prob, header);
+  PCMS_LAUNCH(lt_count_kernel, dim3(nchunks), dim3(TPB), 0, s, labels, offsets, (int)n);
+  PCMS_LAUNCH(lt_scan_kernel, dim3(1), dim3(TPB), 0, s, offsets, nchunks, header);
+  PCMS_LAUNCH(lt_scatter_kernel, dim3(nchunks), dim3(TPB), 0, s, labels, (const int*)offsets, rank, t.label, capacity,
+              (int)n);
   if (with_prob) {
-    LT_LAUNCH(lt_accum_kernel<true>, dim3(nchunks), dim3(TPB), 0, s, labels, prob, (const int*)rank, t, capacity,
-              header, H, W, (int)n);
-    LT_LAUNCH(lt_decode_kernel, dim3(rows), dim3(TPB), 0, s, t, capacity);
+    PCMS_LAUNCH(lt_accum_kernel<true>, dim3(nchunks), dim3(TPB), 0, s, labels, prob, (const int*)rank, t, capacity,
+                header, H, W, (int)n);
+    PCMS_LAUNCH(lt_decode_kernel, dim3(rows), dim3(TPB), 0, s, t, capacity);
   } else {
-    LT_LAUNCH(lt_accum_kernel<false>, dim3(nchunks), dim3(TPB), 0, s, labels, (const float*)nullptr, (const int*)rank,
-              t, capacity, header, H, W, (int)n);
+    PCMS_LAUNCH(lt_accum_kernel<false>, dim3(nchunks), dim3(TPB), 0, s, labels, (const float*)nullptr,
+                (const int*)rank, t, capacity, header, H, W, (int)n);
   }
   return 0;
 }

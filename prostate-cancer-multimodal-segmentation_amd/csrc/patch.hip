@@ -27,7 +27,6 @@ constexpr int CHUNK = TPB * 16;        // voxels per counting chunk: four 16-byt
 constexpr int WAVE_SPAN = CHUNK / WAVES;  // consecutive voxels one wave of the pick re-reads
 constexpr int STEPS = WAVE_SPAN / 64;     // ... in this many 64-lane steps
 
-inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p) % a != 0; }
 inline long chunks_of(long n) { return (n + CHUNK - 1) / CHUNK; }
 
 __device__ __forceinline__ int wave_sum_int(int v) {

@@ -177,8 +177,6 @@ __global__ void __launch_bounds__(TPB) flip_mean_kernel(const float* __restrict_
   }
 }
 
-inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p) % a != 0; }
-
 }  // namespace
 
 extern "C" {

@@ -172,8 +172,6 @@ __global__ void __launch_bounds__(TPB) window_finish_kernel(const float* __restr
   }
 }
 
-inline bool misaligned(const void* p, size_t a) { return ((uintptr_t)p) % a != 0; }
-
 // the k host flip sets as one word; false for a set outside 0..7 or a first set that is not 0
 inline bool pack_flips(const int* flipmask, int k, unsigned* packed) {
   *packed = 0;

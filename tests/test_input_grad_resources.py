@@ -20,7 +20,8 @@ from tests.test_kernel_resources import CSRC, HIPCC, _meta
 
 KERNELS = {
     "stem_dgrad.hip": {"stem_dgrad_mfma_kernel": 512, "stem_dgrad_plain_kernel": 256, "stem_dgrad_pack_kernel": 128},
-    "ops.hip": {"bn_relu_bwd_eval_kernel": 128, "head_bn_bwd_eval_kernel": 128},
+    "ops_bn.hip": {"bn_relu_bwd_eval_kernel": 128},
+    "ops_head.hip": {"head_bn_bwd_eval_kernel": 128},
 }
 
 

@@ -26,7 +26,8 @@ KERNELS = {
     "stem.hip": ["stem_fwd_direct_kernelILi2ELi3E", "stem_fwd_direct_kernelILi3ELi2E", "stem_wgrad_stream_kernel"],
     "convt.hip": ["convt_lds_kernel", "convt_fwd_stream_kernel"],
     # streaming fusions: a spill there would add scratch traffic to an HBM-bound pass
-    "ops.hip": ["maxpool_bwd_bn_kernel", "head_bwd_kernel", "head_bn_apply_kernel", "bn_relu_pool_kernel"],
+    "ops_pool.hip": ["maxpool_bwd_bn_kernel", "bn_relu_pool_kernel"],
+    "ops_head.hip": ["head_bwd_kernel", "head_bn_apply_kernel"],
 }
 # (the 4-deep 16x16x32 conv runs one 256-thread workgroup per CU: one wave per SIMD)
 VGPR_BUDGET = {"convt_lds_kernel": 128, "conv3_fwd_b16_kernelILb0ELi4ELi4E": 512, "conv3_fwd_b16_kernelILb1ELi4ELi4E": 512,

@@ -1,5 +1,6 @@
-"""The streaming kernels of csrc/ops.hip (BatchNorm + ReLU forward / backward, the pool fusions,
-the 1x1x1 head, the loss, Adam, the gradient clip, pack / unpack / add) in the regimes the
+"""The streaming kernels of csrc/ops_bn.hip (BatchNorm + ReLU forward / backward), ops_pool.hip
+(the pool fusions), ops_head.hip (the 1x1x1 head), ops_update.hip (the loss, Adam, the gradient
+clip) and ops_layout.hip (pack / unpack / add) in the regimes the
 product runs them in: several trips per thread under a capped grid (unrolled main loop + tail,
 ``VoxQR`` steps across sample boundaries) and both finalize paths of the partial-row reductions
 (split at 512 rows; ``colsum2_kernel``'s 4-rows-in-flight loop from 769 rows).
