@@ -669,6 +669,47 @@ int pcms_patch_resample_linear(const void* src, int datatype, int Di, int Hi, in
                                int Gd, int Gh, int Gw, const int* origins, int P, float* out, long patch_stride, int D,
                                int H, int W, hipStream_t s);
 
+/* ---- percentile intensity window: predict.py's intensity_window / normalise_window --------- */
+/* predict.intensity_window on the device, bit for bit: lohi[0] / lohi[1] (DEVICE floats) are the
+ * values at ranks r_lo / r_hi of the ascending order of the selected voxels.  A voxel is decoded as
+ * pcms_volume_minmax decodes it and replaced by v + 0.f (-0 becomes +0); the selected set is every
+ * voxel, or with use_above != 0 the voxels with v > above (never a NaN); m is its size.  ppm_lo <
+ * ppm_hi are the two percentiles in parts per million (0 .. 1000000) and r_lo = floor(ppm_lo
+ * (m - 1) / 10^6), r_hi = ceil(ppm_hi (m - 1) / 10^6) in 64-bit integers, formed on the device.
+ * NaNs order last (a selected NaN reads back as a quiet NaN); m == 0 gives (0, 0).  (0, 1000000)
+ * gives pcms_volume_minmax's pair on a NaN-free volume.
+ * Method: a most-significant-digit radix select of both ranks at once on the order-preserving
+ * u32 image of the value (every NaN the top key), 8 bits per pass: one launch zeroes work, then
+ * four times a histogram launch (16-byte loads on the aligned body, a grid capped through
+ * pcms_stream_grid_cap; per workgroup a 2 x 256-bin LDS histogram whose adds are aggregated over
+ * the wave's lanes that share a bin, then one integer atomic per non-empty bin into one of eight
+ * copies of the rows in work) and a one-workgroup launch that sums the copies, scans the bins
+ * and fixes the next digit and the rank left inside it.
+ * Integer counts only: the same bits on every run.  Everything is enqueued on s: no allocation,
+ * no host synchronisation; work is pcms_volume_window_work_bytes(n) bytes of DEVICE memory,
+ * 8-byte aligned, in any state (negative for n < 1 or n >= 2^31).  src needs its element's
+ * alignment only.  An unknown datatype, n < 1 or n >= 2^31, a NULL or misaligned pointer, ppm_lo
+ * < 0, ppm_hi > 1000000, ppm_lo >= ppm_hi, a non-finite above with use_above: negative, no
+ * launch.                                                                                      */
+int pcms_volume_window_work_bytes(long n);
+int pcms_volume_window(const void* src, int datatype, long n, double scl_slope, double scl_inter, int ppm_lo,
+                       int ppm_hi, int use_above, float above, float* lohi, void* work, hipStream_t s);
+/* pcms_resample_linear_norm with predict.normalise_window's corner: with lo = lohi[0], hi =
+ * lohi[1] (DEVICE floats, e.g. pcms_volume_window's) and den = fl32((double)hi - (double)lo), a
+ * source voxel v becomes c = v < lo ? lo : v > hi ? hi : v (a NaN stays), then fl32(fl32(c - lo)
+ * / den), or 0 when den == 0.  Equal to data.resample(predict.normalise_window(vol, lohi), (D, H,
+ * W)) bit for bit.  Rejects what pcms_resample_linear_norm rejects.                            */
+int pcms_resample_linear_window(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
+                                double scl_inter, const float* lohi, float* out, int D, int H, int W, hipStream_t s);
+/* pcms_patch_resample_linear with that corner: data.resample_patch of
+ * predict.normalise_window(vol, lohi), bit for bit.  lohi is required; every other argument, the
+ * 16-byte / scalar store rule and the rejections are pcms_patch_resample_linear's, and a NULL
+ * lohi is rejected too.                                                                        */
+int pcms_patch_resample_window(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
+                               double scl_inter, const double* affine12, const float* lohi, float gain, float bias,
+                               int Gd, int Gh, int Gw, const int* origins, int P, float* out, long patch_stride, int D,
+                               int H, int W, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

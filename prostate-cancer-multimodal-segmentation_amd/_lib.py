@@ -144,6 +144,10 @@ SIGNATURES = {
     "pcms_foreground_pick_work_ints": "l",
     "pcms_foreground_pick": "pliiiiiippipps",  # rank_u (fp64), fallback (int32): device pointers
     "pcms_patch_resample_linear": "piiiiddppffiiipipliiis",  # affine12: host; lohi (or None), origins: device
+    "pcms_volume_window_work_bytes": "l",
+    "pcms_volume_window": "pilddiiifpps",  # ppm_lo, ppm_hi, use_above, above; lohi, work: device pointers
+    "pcms_resample_linear_window": "piiiiddppiiis",
+    "pcms_patch_resample_window": "piiiiddppffiiipipliiis",  # as pcms_patch_resample_linear, lohi required
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

@@ -1,5 +1,6 @@
 // What the resampling kernels of resample.hip (loader, augmentation), deform.hip (elastic
-// augmentation), predict.hip (case prediction) and patch.hip (patch training) share: the per-axis geometry and the 8-corner
+// augmentation), predict.hip (case prediction), patch.hip (patch training) and intensity.hip
+// (percentile intensity window) share: the per-axis geometry and the 8-corner
 // gather of data.resample, the coordinate, inside rules and gather of data.resample_affine,
 // read_nifti's decoding of a voxel and the dispatch over the NIfTI datatype codes.  Every product and sum must
 // round on its own, as numpy's do: no contraction into FMAs from here to the end of the

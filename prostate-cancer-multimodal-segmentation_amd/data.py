@@ -552,13 +552,15 @@ class PatchSampling:
     predictor, every axis a multiple of 16 because the network pools four times -- cut from
     ``grid``, the case grid the windows slide over (``None``: the shape of the case's label
     file).  A share ``foreground_prob`` of them is centred on a lesion voxel (``draw_patches``,
-    ``pick_origins``).  ``normalise``: every modality is min-max normalised over its whole volume
-    first, as ``predict.prepare_case`` does.  ``seed`` seeds the patch draws."""
+    ``pick_origins``).  ``normalise``: every modality is normalised over its whole volume first, as
+    ``predict.prepare_case`` does: ``True`` is min-max (and stays ``True``); a method name
+    (``"percentile"``), a dict or a ``predict.Normalisation`` is kept as a ``Normalisation``.
+    ``seed`` seeds the patch draws."""
     patch_size: Tuple[int, int, int] = (16, 128, 128)
     patches_per_case: int = 2
     foreground_prob: float = 0.5
     grid: Optional[Tuple[int, int, int]] = None
-    normalise: bool = False
+    normalise: object = False
     seed: int = 0
 
     @staticmethod
@@ -583,7 +585,11 @@ class PatchSampling:
             self.grid = _axes3(self.grid, "PatchSampling.grid")
             if min(self.grid) < 1:
                 raise ValueError(f"PatchSampling.grid: every axis is at least 1, got {self.grid}")
-        self.normalise = bool(self.normalise)
+        if isinstance(self.normalise, (str, dict)) or dataclasses.is_dataclass(self.normalise):
+            from .predict import Normalisation
+            self.normalise = Normalisation.of(self.normalise)  # ValueError for an unknown method
+        else:
+            self.normalise = bool(self.normalise)
         self.seed = int(self.seed)
 
 
@@ -604,7 +610,7 @@ def _resample_patch(vol: np.ndarray, grid, A, t, origin, patch, gain, bias) -> n
 
 
 def resample_patch(vol: np.ndarray, grid, A, t, origin, patch, gain: float = 1.0, bias: float = 0.0,
-                   normalise: bool = False) -> np.ndarray:
+                   normalise=False) -> np.ndarray:
     """One ``patch`` = (wd, wh, ww) crop of ``resample_affine(vol, grid, A, t, gain=gain,
     bias=bias)`` at ``origin``, bit for bit, formed from the patch's coordinates alone: patch
     index (d, h, w) stands for grid index ``p = (d, h, w) + origin`` (integers, exact in fp64) and
@@ -613,11 +619,14 @@ def resample_patch(vol: np.ndarray, grid, A, t, origin, patch, gain: float = 1.0
     ``p_a < 0`` or ``p_a >= grid[a]``: a patch that sticks out of the grid is zero-padded, as
     ``predict.gather_windows`` pads a window.  ``normalise``: ``vol`` is first replaced by
     ``predict.normalise(vol)`` (min-max over the whole volume, the corner rule of
-    pcms_resample_linear_norm).  libpcms_hip's pcms_patch_resample_linear restates this per voxel
-    and is compared with it on the fp32 bits."""
-    if normalise:
-        from .predict import normalise as _normalise
-        vol = _normalise(vol)
+    pcms_resample_linear_norm); anything else ``predict.Normalisation.of`` accepts selects that
+    normalisation (``"percentile"``: ``predict.normalise_window`` at the volume's
+    ``predict.intensity_window``).  libpcms_hip's pcms_patch_resample_linear and
+    pcms_patch_resample_window restate this per voxel and are compared with it on the fp32 bits."""
+    from .predict import Normalisation
+    norm = Normalisation.of(normalise)
+    if norm is not None:
+        vol = norm.apply(vol)
     return _resample_patch(vol, grid, A, t, origin, patch, gain, bias)
 
 
@@ -802,8 +811,10 @@ def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
     chooses the P origins there (``picks``: the origins, then the foreground count) and nothing
     brings them back -- pcms_patch_resample_linear reads them from device memory, once per present
     modality into that channel of the case's P patches (after pcms_volume_minmax with
-    ``normalise``; ``None`` channels are zeroed), and one pcms_window_gather cuts the label
-    patches.  Everything is enqueued on the current stream, with no host synchronisation."""
+    ``normalise``, or after pcms_volume_window and through pcms_patch_resample_window when the
+    batch's ``"normalise"`` entry selects the percentile window; ``None`` channels are zeroed),
+    and one pcms_window_gather cuts the label patches.  Everything is enqueued on the current
+    stream, with no host synchronisation."""
     from ._lib import call, query
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
@@ -811,7 +822,9 @@ def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
                            "pcms_amd has no CPU resampling kernel (use the default loader there)")
     images, labels, draws = raw_batch["raw_images"], raw_batch["raw_label"], raw_batch["patches"]
     patch = tuple(int(v) for v in raw_batch["patch_size"])
-    normalise = bool(raw_batch["normalise"])
+    from .predict import Normalisation, _lohi_enqueue
+    norm = Normalisation.of(raw_batch["normalise"])
+    normalise = norm is not None
     n, m = len(images), len(images[0])
     P = int(draws[0]["rank_u"].numel())
     nwin = patch[0] * patch[1] * patch[2]
@@ -846,13 +859,12 @@ def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
                 if raw.data.dtype != torch.uint8 or raw.data.numel() != cnt * np.dtype(_NIFTI_DTYPES[raw.code]).itemsize:
                     raise ValueError(f"RawVolume holds {raw.data.numel()} bytes, shape {raw.shape} of datatype "
                                      f"{raw.code} needs {cnt * np.dtype(_NIFTI_DTYPES[raw.code]).itemsize}")
-                if normalise:
-                    mm = torch.empty(query("pcms_volume_minmax_work_floats", cnt), dtype=torch.float32, device=device)
-                    call("pcms_volume_minmax", raw.data, int(raw.code), cnt, float(raw.slope), float(raw.inter), lohi, mm)
+                # the window is formed once per volume and read from device memory by every patch
+                windowed = normalise and _lohi_enqueue(raw, norm, lohi) == "window"
                 host = (ctypes.c_double * 12)(*(float(v) for v in d["affine"][c]))  # read during the call
-                call("pcms_patch_resample_linear", raw.data, int(raw.code), *raw.shape, float(raw.slope),
-                     float(raw.inter), ctypes.addressof(host), lohi, float(d["gain"][c]), float(d["bias"][c]), *grid,
-                     picks[i], P, first, m * nwin, *patch)
+                call("pcms_patch_resample_window" if windowed else "pcms_patch_resample_linear", raw.data,
+                     int(raw.code), *raw.shape, float(raw.slope), float(raw.inter), ctypes.addressof(host), lohi,
+                     float(d["gain"][c]), float(d["bias"][c]), *grid, picks[i], P, first, m * nwin, *patch)
             call("pcms_window_gather", label_grid, 1, *grid, picks[i], P, ctypes.addressof(no_flip), 1, *patch,
                  label[i * P:(i + 1) * P])
     return {"image": image, "label": label, "case_id": [cid for cid in raw_batch["case_id"] for _ in range(P)],
@@ -1058,7 +1070,7 @@ class ProstateDataset(Dataset):
                      # CPU tensors, so that the DataLoader's pin_memory handles them
                      "rank_u": torch.from_numpy(rank_u), "fallback": torch.from_numpy(fallback)}
             return {"raw_images": raws, "raw_label": lab, "case_id": case["case_id"], "patches": draws}
-        from .predict import gather_windows, normalise
+        from .predict import Normalisation, gather_windows
         lab = self._first_volume(read_nifti(case["label_path"]))
         grid = ps.grid if ps.grid is not None else tuple(lab.shape)
         rank_u, fallback = draw_patches(ps, ps.seed, self.epoch, idx, grid)
@@ -1072,7 +1084,7 @@ class ProstateDataset(Dataset):
                 continue
             vol = self._first_volume(read_nifti(p)).astype(np.float32)
             if ps.normalise:  # once per volume, not per patch
-                vol = normalise(vol)
+                vol = Normalisation.of(ps.normalise).apply(vol)
             A, t = tf.affine(vol.shape, grid)
             for k in range(P):
                 image[k, c] = _resample_patch(vol, grid, A, t, origins[k], ps.patch_size, tf.gain[c], tf.bias[c])

@@ -39,6 +39,12 @@ a volume into fixed-size overlapping windows and blending the windows' probabili
 centre-weighted weights; ``gather_windows_device`` / ``blend_windows_device`` /
 ``sliding_window_device`` run them in HIP kernels, bit for bit and independent of the batching;
 ``predict_case(..., window=...)`` predicts a case at its native resolution through them.
+
+Percentile intensity normalisation: ``intensity_window`` / ``normalise_window`` are
+the host forms of a robust window -- two exact order statistics of a volume, the volume clipped to
+them and scaled to [0, 1]; ``Normalisation`` names the choice wherever ``normalise`` is taken
+(``True`` stays min-max); on the device pcms_volume_window selects the window from the raw bytes
+and the ``_window`` resampling kernels consume it, bit for bit.
 """
 from __future__ import annotations
 
@@ -101,6 +107,130 @@ def normalise(vol: np.ndarray) -> np.ndarray:
 _normalise = normalise  # prepare_case's keyword of the same name shadows the function there
 
 
+def _window_ppm(lower: float, upper: float) -> Tuple[int, int]:
+    """The two percentiles in parts per million, as integers; ValueError unless
+    ``0 <= q_lo < q_hi <= 1_000_000``."""
+    try:
+        q_lo, q_hi = int(round(float(lower) * 10000)), int(round(float(upper) * 10000))
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"percentiles are two numbers with 0 <= lower < upper <= 100, got {lower!r}, "
+                         f"{upper!r}") from None
+    if not 0 <= q_lo < q_hi <= 1_000_000:
+        raise ValueError(f"percentiles need 0 <= lower < upper <= 100, got {lower!r}, {upper!r}")
+    return q_lo, q_hi
+
+
+def _window_above(above) -> Optional[float]:
+    if above is None:
+        return None
+    a = float(np.float32(above))
+    if not math.isfinite(a):
+        raise ValueError(f"above is None or a finite number, got {above!r}")
+    return a
+
+
+def intensity_window(vol: np.ndarray, lower: float = 0.5, upper: float = 99.5, above=None) -> np.ndarray:
+    """The robust intensity window ``[lo, hi]`` of one volume, two float32 values: exact order
+    statistics, no interpolation.  ``v = vol.astype(float32) + float32(0)`` (the sum folds -0.0
+    into +0.0); the selected set is all of ``v``, or ``v[v > float32(above)]`` (never a NaN); ``m``
+    is its size and ``m == 0`` gives ``[0, 0]``.  The percentiles become integers,
+    ``q = int(round(p * 10000))`` parts per million with ``0 <= q_lo < q_hi <= 1_000_000``
+    (ValueError), and so do the ranks: ``r_lo = (q_lo * (m - 1)) // 10**6`` and
+    ``r_hi = ceil(q_hi * (m - 1) / 10**6)``.  ``s = np.sort(selected)`` (NaNs last):
+    ``lo = s[r_lo]``, ``hi = s[r_hi]``.  ``lower=0, upper=100`` is the minimum and maximum of a
+    NaN-free volume.  libpcms_hip's pcms_volume_window is compared with this on the bits."""
+    q_lo, q_hi = _window_ppm(lower, upper)
+    above = _window_above(above)
+    v = np.asarray(vol).astype(np.float32).reshape(-1) + np.float32(0)
+    if above is not None:
+        with np.errstate(invalid="ignore"):
+            v = v[v > np.float32(above)]
+    m = int(v.size)
+    if m == 0:
+        return np.zeros(2, dtype=np.float32)
+    r_lo = (q_lo * (m - 1)) // 10 ** 6
+    r_hi = -((-q_hi * (m - 1)) // 10 ** 6)
+    s = np.sort(v)
+    return np.array([s[r_lo], s[r_hi]], dtype=np.float32)
+
+
+def normalise_window(vol: np.ndarray, lohi) -> np.ndarray:
+    """``vol`` clipped to the window ``lohi = (lo, hi)`` and scaled to [0, 1], float32:
+    ``den = float32(float64(hi) - float64(lo))``; zeros when ``den == 0``; else ``c`` is ``lo``
+    where ``v < lo``, ``hi`` where ``v > hi`` and ``v`` elsewhere -- comparisons, not min / max, so
+    a NaN voxel stays NaN -- and the result is ``(c - lo) / den`` in fp32.  With
+    ``lohi = (v.min(), v.max())`` of a NaN-free volume this is ``normalise`` bit for bit."""
+    v = np.asarray(vol).astype(np.float32)
+    lo, hi = (np.float32(x) for x in np.asarray(lohi, dtype=np.float32).reshape(2))
+    with np.errstate(over="ignore", invalid="ignore"):
+        den = np.float32(np.float64(hi) - np.float64(lo))
+        if den == 0:
+            return np.zeros_like(v)
+        c = np.where(v < lo, lo, np.where(v > hi, hi, v))
+        return (c - lo) / den
+
+
+@dataclasses.dataclass
+class Normalisation:
+    """How a volume's intensities are brought to [0, 1] before resampling.  ``method``:
+    ``"minmax"`` (``normalise``, what the reference's ``load_multimodal_images`` does) or
+    ``"percentile"`` (``normalise_window`` of ``intensity_window(vol, lower, upper, above)``: the
+    percentile window of the voxels above ``above``, or of all voxels with ``above=None``)."""
+    method: str = "minmax"
+    lower: float = 0.5
+    upper: float = 99.5
+    above: Optional[float] = None
+
+    METHODS = ("minmax", "percentile")
+
+    @staticmethod
+    def of(x) -> Optional["Normalisation"]:
+        """``False`` / ``None``: no normalisation (None); ``True``: min-max; a method name, a
+        dict of the fields or an instance."""
+        if x is None or isinstance(x, Normalisation):
+            return x
+        if isinstance(x, (bool, np.bool_, int)):
+            return Normalisation() if x else None
+        if isinstance(x, str):
+            return Normalisation(method=x)
+        if isinstance(x, dict):
+            return Normalisation(**x)
+        raise ValueError(f"normalise is False, True, a method name, a dict or a Normalisation, got {x!r}")
+
+    def __post_init__(self):
+        if self.method not in self.METHODS:
+            raise ValueError(f"unknown normalisation method {self.method!r}: one of {self.METHODS}")
+        self.ppm = _window_ppm(self.lower, self.upper)
+        self.lower, self.upper = float(self.lower), float(self.upper)
+        self.above = _window_above(self.above)
+
+    def apply(self, vol: np.ndarray) -> np.ndarray:
+        """The normalised volume, float32 (the host form of both device paths)."""
+        if self.method == "minmax":
+            return normalise(vol)
+        return normalise_window(vol, intensity_window(vol, self.lower, self.upper, self.above))
+
+
+def _lohi_enqueue(raw, norm: Normalisation, lohi: torch.Tensor) -> str:
+    """Enqueue the kernel that leaves ``norm``'s (lo, hi) of the raw volume in the two device
+    floats ``lohi``: pcms_volume_minmax or pcms_volume_window.  Returns the suffix of the
+    consumers that read it: ``"norm"`` (pcms_resample_linear_norm, pcms_patch_resample_linear
+    with lohi) or ``"window"`` (pcms_resample_linear_window, pcms_patch_resample_window)."""
+    from ._lib import call, query
+    n = int(np.prod(raw.shape))
+    if norm.method == "minmax":
+        work = torch.empty(query("pcms_volume_minmax_work_floats", n), dtype=torch.float32, device=lohi.device)
+        call("pcms_volume_minmax", raw.data, int(raw.code), n, float(raw.slope), float(raw.inter), lohi, work)
+        return "norm"
+    nbytes = query("pcms_volume_window_work_bytes", n)
+    if nbytes < 0:
+        raise ValueError(f"a volume of {n} voxels is outside pcms_volume_window's range")
+    work = torch.empty(nbytes // 8, dtype=torch.int64, device=lohi.device)
+    call("pcms_volume_window", raw.data, int(raw.code), n, float(raw.slope), float(raw.inter), norm.ppm[0], norm.ppm[1],
+         0 if norm.above is None else 1, 0.0 if norm.above is None else norm.above, lohi, work)
+    return "window"
+
+
 def _case_files(case_dir: str) -> List[Optional[str]]:
     """Per modality the first ``.nii`` of its folder in sorted order, or None."""
     paths = []
@@ -140,14 +270,17 @@ def _first_volume(a: np.ndarray) -> np.ndarray:
 
 
 def prepare_case(case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
-                 handle_missing: str = "zero_fill", normalise: bool = True) -> np.ndarray:
+                 handle_missing: str = "zero_fill", normalise=True) -> np.ndarray:
     """The five modalities of a case on one grid, (5, D, H, W) float32: per modality the first
     ``.nii`` in sorted order (volume 0 of a 4-D file), ``normalise``d when asked, else as fp32,
     then ``data.resample(., target_size)`` (linear).  A missing modality is zeros
     ('zero_fill'), the first present modality's channel ('duplicate') or an error ('skip').
     ``target_size=None``: no resampling; the present shapes must agree (ValueError).
     With ``normalise=False`` a channel is the one the default training loader forms for the
-    file; with ``normalise=True`` it is ``load_multimodal_images``' channel on the grid."""
+    file; with ``normalise=True`` it is ``load_multimodal_images``' channel on the grid.
+    ``normalise`` is anything ``Normalisation.of`` accepts: ``"percentile"`` (or a dict / a
+    ``Normalisation``) clips every modality to its own percentile window first."""
+    norm = Normalisation.of(normalise)
     paths, grid, dup = _case_plan(case_dir, target_size, handle_missing)
     chans: List[Optional[np.ndarray]] = []
     for p in paths:
@@ -155,7 +288,7 @@ def prepare_case(case_dir: str, target_size: Optional[Sequence[int]] = (128, 128
             chans.append(None)
             continue
         vol = _first_volume(read_nifti(p))
-        vol = _normalise(vol) if normalise else vol.astype(np.float32)
+        vol = norm.apply(vol) if norm is not None else vol.astype(np.float32)
         chans.append(_data.resample(vol, grid))
     fill = np.zeros(grid, dtype=np.float32) if dup is None else chans[dup]
     return np.stack([fill if c is None else c for c in chans], axis=0)
@@ -1190,13 +1323,16 @@ def sliding_window_device(predict_fn, x: torch.Tensor, window: Sequence[int], ov
 
 
 def prepare_case_device(case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
-                        handle_missing: str = "zero_fill", normalise: bool = True,
+                        handle_missing: str = "zero_fill", normalise=True,
                         device="cuda") -> torch.Tensor:
     """``prepare_case`` on the GPU, bit for bit, as the (1, 5, D, H, W) fp32 network input: each
     file's undecoded bytes (``data.read_nifti_raw``) go up once; pcms_volume_minmax and
-    pcms_resample_linear_norm form the normalised channel, ``data.resample_device`` the plain
-    one.  Everything is enqueued on the current stream."""
-    from ._lib import call, query
+    pcms_resample_linear_norm form the min-max normalised channel, pcms_volume_window and
+    pcms_resample_linear_window the percentile one (the window is computed once per volume and
+    read from device memory), ``data.resample_device`` the plain one.  Everything is enqueued on
+    the current stream."""
+    from ._lib import call
+    norm = Normalisation.of(normalise)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"prepare_case_device needs a GPU, not '{device}': pcms_amd has no CPU fallback -- "
@@ -1209,14 +1345,12 @@ def prepare_case_device(case_dir: str, target_size: Optional[Sequence[int]] = (1
             if p is None:
                 continue
             raw = _data.read_nifti_raw(p).to(device)
-            if not normalise:
+            if norm is None:
                 _data.resample_device(raw, grid, out=x[0, c])
                 continue
-            n = int(np.prod(raw.shape))
-            work = torch.empty(query("pcms_volume_minmax_work_floats", n), dtype=torch.float32, device=device)
-            call("pcms_volume_minmax", raw.data, int(raw.code), n, float(raw.slope), float(raw.inter), lohi, work)
-            call("pcms_resample_linear_norm", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
-                 lohi, x[0, c], *grid)
+            kind = _lohi_enqueue(raw, norm, lohi)
+            call("pcms_resample_linear_" + kind, raw.data, int(raw.code), *raw.shape, float(raw.slope),
+                 float(raw.inter), lohi, x[0, c], *grid)
         for c, p in enumerate(paths):
             if p is None and dup is None:
                 x[0, c].zero_()
@@ -1272,7 +1406,7 @@ class ModelPredictor:
         write_nifti(output_path, (prediction > 0.5).astype(np.uint8), spacing=spacing)
 
     def predict_case(self, case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
-                     handle_missing: str = "zero_fill", normalise: bool = True, threshold: float = 0.5,
+                     handle_missing: str = "zero_fill", normalise=True, threshold: float = 0.5,
                      tta_flips: Sequence[Tuple[int, ...]] = (), output_like: Optional[str] = None,
                      return_probability: bool = False, *, keep_largest: int = 0, min_voxels: int = 0,
                      fill_holes: bool = False, connectivity: int = 26,
@@ -1285,7 +1419,9 @@ class ModelPredictor:
         of the mask to the host (and of the probabilities with ``return_probability``).  The
         native grid is that of ``output_like`` (any NIfTI file, e.g. the label) or else of the
         first present modality's file.  ``normalise=False`` feeds the network what the training
-        loader feeds it; ``normalise=True`` what ``load_multimodal_images`` would, resampled.
+        loader feeds it; ``normalise=True`` what ``load_multimodal_images`` would, resampled;
+        ``"percentile"`` or a ``Normalisation`` the percentile window, here and with
+        ``window``.
         ``keep_largest`` / ``min_voxels`` / ``fill_holes`` / ``connectivity`` (keyword-only): the
         mask goes through pcms_mask_postprocess (``postprocess``) on the device before the copy;
         with their defaults nothing is launched for them.  ``return_lesions=True``: the result's
