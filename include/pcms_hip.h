@@ -710,6 +710,38 @@ int pcms_patch_resample_window(const void* src, int datatype, int Di, int Hi, in
                                int Gd, int Gh, int Gw, const int* origins, int P, float* out, long patch_stride, int D,
                                int H, int W, hipStream_t s);
 
+/* ---- modality alignment: predict.py's joint_histogram ------------------------------------- */
+/* predict.joint_histogram on the device, on the counts exactly: the joint intensity histogram of
+ * a fixed and a moving raw volume under an affine, the table a mutual-information similarity is
+ * formed from.  The lattice is every (sd, sh, sw)-th voxel of the fixed volume, q = (a sd, b sh,
+ * e sw) with q inside (Df, Hf, Wf).  For a lattice voxel q: the moving coordinate is c_a =
+ * ((A[a][0] q_d + A[a][1] q_h) + A[a][2] q_w) + t[a] (fp64, pcms_resample_affine_linear's); the
+ * voxel counts iff -0.5 <= c_a < n_a - 0.5 on all three moving axes and neither value below is a
+ * NaN.  f: the fixed voxel decoded as pcms_resample_linear decodes it, then
+ * pcms_resample_linear_window's corner under flohi (clip to [lo, hi] by comparisons, fl32(fl32(c
+ * - lo) / den), 0 when den == 0).  m: pcms_resample_affine_linear's 8-corner sample (gain 1, bias
+ * 0) of the moving volume's corners treated the same way under mlohi.  The bin of a value v is
+ * (int) of fl32(v * (float)bins) clamped to [0, bins - 1] -- min((int)fl32(v bins), bins - 1) for
+ * v in [0, 1] -- and hist[bf * bins + bm] (bins * bins DEVICE uint32, all of it written) is the
+ * number of counted voxels with that pair; the sum of the table is the overlap count.
+ * flohi / mlohi: two DEVICE floats each (pcms_volume_minmax's or pcms_volume_window's), read on
+ * the device.  affine12: twelve HOST doubles, row-major A then t, read during the call.
+ * Method: one launch zeroes work; one thread per lattice voxel, grid-stride (a grid capped
+ * through pcms_stream_grid_cap), counts into a 64 x 64 table of 32-bit counts in LDS by integer
+ * atomics aggregated over the wave's lanes that share a bin, then one integer atomic per
+ * non-empty bin and workgroup into one of eight copies of the table in work; a third launch sums
+ * the copies into hist.  Integer counts only: the same bits on every run.  Everything is enqueued
+ * on s: no allocation, no host synchronisation; work is pcms_joint_histogram_work_bytes(bins)
+ * bytes of DEVICE memory, 4-byte aligned, in any state (negative for bins outside 2..64).  fix
+ * and mov need their element's alignment only.  bins outside 2..64, a stride or an extent below
+ * 1, a lattice of 2^31 voxels or more, a NULL or misaligned pointer, an unknown datatype, a
+ * non-finite affine: negative, no launch.                                                     */
+int pcms_joint_histogram_work_bytes(int bins);
+int pcms_joint_histogram(const void* fix, int fdatatype, int Df, int Hf, int Wf, double fslope, double finter,
+                         const float* flohi, const void* mov, int mdatatype, int Dm, int Hm, int Wm, double mslope,
+                         double minter, const float* mlohi, const double* affine12, int sd, int sh, int sw, int bins,
+                         unsigned* hist, void* work, hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

@@ -148,6 +148,10 @@ SIGNATURES = {
     "pcms_volume_window": "pilddiiifpps",  # ppm_lo, ppm_hi, use_above, above; lohi, work: device pointers
     "pcms_resample_linear_window": "piiiiddppiiis",
     "pcms_patch_resample_window": "piiiiddppffiiipipliiis",  # as pcms_patch_resample_linear, lohi required
+    "pcms_joint_histogram_work_bytes": "i",
+    # fixed then moving volume (src, datatype, D, H, W, slope, inter, lohi: device), affine12: host;
+    # sd, sh, sw, bins; hist, work: device pointers
+    "pcms_joint_histogram": "piiiiddp" + "piiiiddp" + "p" + "iiii" + "pp" + "s",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

@@ -17,6 +17,7 @@
 #include "resample_common.h"
 
 #include "ops_units.h"
+#include "wave_hist.h"
 #include "pcms_hip.h"
 
 #pragma clang fp contract(off)
@@ -59,22 +60,6 @@ __device__ __forceinline__ uint32_t key_of(float v) {
 __device__ __forceinline__ float value_of(uint32_t k) {
   if (k == 0xffffffffu) return __uint_as_float(0x7fc00000u);
   return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// hist[digit] += 1 for every lane that is `on`.  An MR volume is mostly one value, so most lanes
-// of a wave meet in one bin: the lanes that share the first active lane's bin are counted by a
-// ballot and added once, only the others add for themselves.
-__device__ __forceinline__ void bin_add(uint32_t* hist, uint32_t digit, bool on, int lane) {
-  const unsigned long long active = __ballot(on);
-  if (active == 0) return;  // uniform over the wave
-  const int leader = __ffsll(active) - 1;
-  const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)digit, leader);
-  const bool share = on && digit == d0;
-  const uint32_t lanes = (uint32_t)__popcll(__ballot(share));
-  if (lane == leader)
-    __hip_atomic_fetch_add(hist + d0, lanes, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  else if (on && !share)
-    __hip_atomic_fetch_add(hist + digit, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 __global__ void __launch_bounds__(TPB) window_init_kernel(uint32_t* __restrict__ work, int words) {
@@ -208,14 +193,6 @@ __global__ void __launch_bounds__(TPB) window_scan_kernel(Work* __restrict__ wor
       if (pass == PASSES - 1) lohi[k] = value_of(key);
     }
   }
-}
-
-// normalise_window of one decoded value: the clip written with comparisons (a NaN passes
-// through), then predict.normalise's difference and quotient
-__device__ __forceinline__ float windowed(float v, float lo, float hi, float den) {
-  if (den == 0.f) return 0.f;
-  const float c = v < lo ? lo : v > hi ? hi : v;
-  return (c - lo) / den;
 }
 
 // resample_linear_norm_kernel (predict.hip) with the clipped corner

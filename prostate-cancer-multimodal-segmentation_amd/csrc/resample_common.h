@@ -1,7 +1,7 @@
 // What the resampling kernels of resample.hip (loader, augmentation), deform.hip (elastic
-// augmentation), predict.hip (case prediction), patch.hip (patch training) and intensity.hip
-// (percentile intensity window) share: the per-axis geometry and the 8-corner
-// gather of data.resample, the coordinate, inside rules and gather of data.resample_affine,
+// augmentation), predict.hip (case prediction), patch.hip (patch training), intensity.hip
+// (percentile intensity window) and align.hip (joint histogram) share: the per-axis geometry and
+// the 8-corner gather of data.resample, the coordinate, inside rules and gather of data.resample_affine,
 // read_nifti's decoding of a voxel and the dispatch over the NIfTI datatype codes.  Every product and sum must
 // round on its own, as numpy's do: no contraction into FMAs from here to the end of the
 // including file.
@@ -172,6 +172,14 @@ __device__ __forceinline__ float affine_linear_value(const T* __restrict__ src, 
 // predict.normalise of one decoded value: den = fl32((double)hi - (double)lo), formed per thread
 __device__ __forceinline__ float normalised(float v, float lo, float den) {
   return den == 0.f ? 0.f : (v - lo) / den;
+}
+
+// predict.normalise_window of one decoded value: the clip written with comparisons (a NaN passes
+// through), then predict.normalise's difference and quotient
+__device__ __forceinline__ float windowed(float v, float lo, float hi, float den) {
+  if (den == 0.f) return 0.f;
+  const float c = v < lo ? lo : v > hi ? hi : v;
+  return (c - lo) / den;
 }
 
 // the label at source coordinates (cd, ch, cw): (float)value > 0 of the nearest voxel, the decoded

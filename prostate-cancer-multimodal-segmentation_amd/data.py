@@ -38,6 +38,11 @@ grid, a chosen share centred on a lesion voxel -- ``draw_patches`` / ``pick_orig
 ``resample_patch`` on the host, pcms_foreground_pick / pcms_patch_resample_linear in
 ``assemble_patch_batch``, the origins chosen and consumed on the device; the same batches bit
 for bit once more.
+``align=...`` (a ``predict.Alignment``; dataset, loader, ``Trainer`` config) places every volume of
+a case on the reference file's grid through the files' world geometry instead of stretching it
+onto the grid: ``world_matrix`` / ``align_affine`` / ``compose_affine`` / ``case_affine`` on the
+host, the same twelve doubles per volume in the existing affine launches on the device, with the
+rigid ``corrections`` of ``predict.register_dataset`` when given; the same batches bit for bit.
 The reference's SimpleITK ``SetSize`` takes (x, y, z), so its non-cubic outputs come out
 axis-reversed; here ``target_size`` is (D, H, W) as documented (:41).
 """
@@ -475,6 +480,160 @@ def volume_affine(L, shift, n_in, n_out) -> Tuple[np.ndarray, np.ndarray]:
     return S[:, None] * L + 0.0, S * ((C - LC) - shift) + 0.0
 
 
+# ---- world geometry: where a file's grid lies in space -----------------------------
+# A world matrix is 4x4 fp64 and maps a file's (x, y, z) voxel index (homogeneous) to millimetres.
+# Arrays are (z, y, x), so an array-order affine is P . M . P with P the x<->z swap.  All products
+# below are written out (no BLAS): the same doubles wherever they are formed.
+def _matmul4(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    return np.array([[((a[i, 0] * b[0, j] + a[i, 1] * b[1, j]) + a[i, 2] * b[2, j]) + a[i, 3] * b[3, j]
+                      for j in range(4)] for i in range(4)])
+
+
+def _affine_inverse4(w: np.ndarray, what: str) -> np.ndarray:
+    """The inverse of a 4x4 affine (last row 0 0 0 1) by the adjugate of its 3x3 part; ValueError
+    when that part is singular or not finite."""
+    m = w[:3, :3]
+    c = np.array([[m[(i + 1) % 3, (j + 1) % 3] * m[(i + 2) % 3, (j + 2) % 3]
+                   - m[(i + 1) % 3, (j + 2) % 3] * m[(i + 2) % 3, (j + 1) % 3] for j in range(3)] for i in range(3)])
+    det = (m[0, 0] * c[0, 0] + m[0, 1] * c[0, 1]) + m[0, 2] * c[0, 2]
+    if not np.isfinite(w).all() or det == 0.0:
+        raise ValueError(f"{what}: the world matrix is singular or not finite")
+    inv = np.eye(4)
+    inv[:3, :3] = c.T / det
+    inv[:3, 3] = [-((inv[i, 0] * w[0, 3] + inv[i, 1] * w[1, 3]) + inv[i, 2] * w[2, 3]) for i in range(3)]
+    return inv + 0.0
+
+
+def world_matrix(geometry: dict) -> np.ndarray:
+    """The (4, 4) fp64 matrix that maps a file's (x, y, z) voxel index to millimetres, from a
+    ``read_nifti_geometry`` dict, formed in fp64 from the header's float32 fields.  Precedence:
+    the sform rows (``srow_x/y/z``) when ``sform_code > 0``; else, when ``qform_code > 0``, the
+    NIfTI-1 quaternion form -- ``a = sqrt(1 - b^2 - c^2 - d^2)`` (0 when the sum exceeds 1), the
+    rotation of (a, b, c, d), its columns scaled by ``pixdim[1..3]``, the third also by ``qfac =
+    pixdim[0]`` (-1 only when the field is exactly -1, else +1), the offset ``qoffset_x/y/z``;
+    else ``diag(pixdim[1..3])`` with a zero offset."""
+    g = geometry
+    w = np.eye(4)
+    pix = [float(v) for v in g["pixdim"]]
+    if int(g["sform_code"]) > 0:
+        for i, name in enumerate(("srow_x", "srow_y", "srow_z")):
+            w[i, :] = [float(v) for v in g[name]]
+        return w
+    if int(g["qform_code"]) > 0:
+        b, c, d = float(g["quatern_b"]), float(g["quatern_c"]), float(g["quatern_d"])
+        a2 = 1.0 - (b * b + c * c + d * d)
+        a = float(np.sqrt(a2)) if a2 > 0.0 else 0.0
+        r = np.array([[a * a + b * b - c * c - d * d, 2.0 * (b * c - a * d), 2.0 * (b * d + a * c)],
+                      [2.0 * (b * c + a * d), a * a + c * c - b * b - d * d, 2.0 * (c * d - a * b)],
+                      [2.0 * (b * d - a * c), 2.0 * (c * d + a * b), a * a + d * d - b * b - c * c]])
+        qfac = -1.0 if pix[0] == -1.0 else 1.0
+        w[:3, :3] = r * np.array([pix[1], pix[2], pix[3] * qfac])
+        w[:3, 3] = [float(g["qoffset_x"]), float(g["qoffset_y"]), float(g["qoffset_z"])]
+        return w + 0.0
+    w[0, 0], w[1, 1], w[2, 2] = pix[1], pix[2], pix[3]
+    return w
+
+
+RIGID_NAMES = ("tz", "ty", "tx", "rz", "ry", "rx")  # millimetres, then degrees
+
+
+def rigid_world(params, centre_xyz) -> np.ndarray:
+    """The (4, 4) rigid motion of six parameters ``(tz, ty, tx mm; rz, ry, rx degrees)`` in world
+    millimetres about the world point ``centre_xyz``: ``x -> R (x - c) + c + (tx, ty, tz)`` with
+    ``R = R_z(rz) . R_y(ry) . R_x(rx)``, each a right-handed rotation about that world axis."""
+    tz, ty, tx, rz, ry, rx = (float(v) for v in params)
+    az, ay, ax = (float(np.deg2rad(v)) for v in (rz, ry, rx))
+    c, s = np.cos, np.sin
+    mz = np.array([[c(az), -s(az), 0.0], [s(az), c(az), 0.0], [0.0, 0.0, 1.0]])
+    my = np.array([[c(ay), 0.0, s(ay)], [0.0, 1.0, 0.0], [-s(ay), 0.0, c(ay)]])
+    mx = np.array([[1.0, 0.0, 0.0], [0.0, c(ax), -s(ax)], [0.0, s(ax), c(ax)]])
+    r = _matmul3(_matmul3(mz, my), mx)
+    cen = np.asarray(centre_xyz, dtype=np.float64).reshape(3)
+    rc = np.array([(r[i, 0] * cen[0] + r[i, 1] * cen[1]) + r[i, 2] * cen[2] for i in range(3)])
+    m = np.eye(4)
+    m[:3, :3] = r
+    m[:3, 3] = (cen - rc) + np.array([tx, ty, tz])
+    return m + 0.0
+
+
+def world_centre(geometry: dict, shape_zyx) -> np.ndarray:
+    """The world position (x, y, z mm) of the centre ``(n - 1) / 2`` of a (z, y, x) grid."""
+    w = world_matrix(geometry)
+    i = np.array([(float(n) - 1.0) / 2.0 for n in tuple(shape_zyx)[::-1]])
+    return np.array([((w[a, 0] * i[0] + w[a, 1] * i[1]) + w[a, 2] * i[2]) + w[a, 3] for a in range(3)])
+
+
+def rigid_correction(params, ref_geometry: dict, ref_shape) -> np.ndarray:
+    """``rigid_world`` of ``params`` about the centre of the reference grid: the ``correction``
+    ``align_affine`` takes for a ``predict.register_rigid`` result."""
+    return rigid_world(params, world_centre(ref_geometry, ref_shape))
+
+
+def align_affine(ref_geometry: dict, mov_geometry: dict, correction=None) -> Tuple[np.ndarray, np.ndarray]:
+    """``(A, t)`` in array order (z, y, x) that takes an array index of the reference file to the
+    array index of the same world point in the moving file: ``P . inv(W_mov) . [T] . W_ref . P``
+    with ``W`` the ``world_matrix`` of each file, ``P`` the x<->z swap and ``T`` an optional (4, 4)
+    rigid ``correction`` in world millimetres (``rigid_correction``: reference world -> moving
+    world).  A singular ``W_mov`` raises ValueError.  Without a correction and with two world
+    matrices equal element for element the result is exactly ``(I, 0)``.  A reference voxel whose
+    image lies outside the moving grid reads 0 in every resampler (the outside rule of
+    ``resample_affine``)."""
+    w_ref, w_mov = world_matrix(ref_geometry), world_matrix(mov_geometry)
+    inv = _affine_inverse4(w_mov, "align_affine")
+    if correction is None and np.array_equal(w_ref, w_mov):
+        return np.eye(3), np.zeros(3)
+    m = w_ref
+    if correction is not None:
+        T = np.asarray(correction, dtype=np.float64)
+        if T.shape != (4, 4) or not np.isfinite(T).all():
+            raise ValueError(f"correction is a finite (4, 4) matrix, got {correction!r}")
+        m = _matmul4(T, m)
+    m = _matmul4(inv, m)
+    return m[:3, :3][::-1, ::-1] + 0.0, m[:3, 3][::-1] + 0.0
+
+
+def compose_affine(first, second) -> Tuple[np.ndarray, np.ndarray]:
+    """``(A, t)`` of ``x -> second(first(x))`` for two ``(A, t)`` pairs, in fp64 with every product
+    and sum written out: ``A = A2 . A1``, ``t = A2 . t1 + t2``.  An identity ``second`` gives
+    ``first`` back exactly."""
+    A1, t1 = np.asarray(first[0], dtype=np.float64).reshape(3, 3), np.asarray(first[1], dtype=np.float64).reshape(3)
+    A2, t2 = np.asarray(second[0], dtype=np.float64).reshape(3, 3), np.asarray(second[1], dtype=np.float64).reshape(3)
+    A = _matmul3(A2, A1)
+    t = np.array([((A2[i, 0] * t1[0] + A2[i, 1] * t1[1]) + A2[i, 2] * t1[2]) + t2[i] for i in range(3)])
+    return A + 0.0, t + 0.0
+
+
+def case_affine(L, shift, n_in, n_out, alignment=None) -> Tuple[np.ndarray, np.ndarray]:
+    """One volume's ``(A, t)`` from the case grid ``n_out`` into the volume's own array: the one
+    function every loader, host or device, forms it with.  Without ``alignment`` it is
+    ``volume_affine(L, shift, n_in, n_out)``: the file stretched onto the grid.  ``alignment`` is
+    ``(ref_shape, (A, t))``: the case grid is scaled onto the reference file's native grid
+    (``volume_affine`` with the reference's shape) and that is composed with the ``align_affine``
+    pair into this volume; ``n_in`` then plays no part."""
+    if alignment is None:
+        return volume_affine(L, shift, n_in, n_out)
+    ref_shape, pair = alignment
+    return compose_affine(volume_affine(L, shift, tuple(int(v) for v in ref_shape), n_out), pair)
+
+
+def affine12_of(A, t) -> Tuple[float, ...]:
+    """``(A, t)`` as the twelve doubles the C entry points take: row-major A, then t."""
+    return tuple(float(v) for v in np.asarray(A).reshape(-1)) + tuple(float(v) for v in np.asarray(t).reshape(-1))
+
+
+def registration_fixed(modalities: Sequence[str], present, to: Optional[str]) -> str:
+    """The modality the others of a case are registered to, and about whose centre their rigid
+    corrections turn: ``to`` when it names a present modality, else the first present one in
+    ``modalities`` order (a label or any other file only lends its grid)."""
+    if to in modalities and to in present:
+        return to
+    return next(m for m in modalities if m in present)
+
+
+def _shape_zyx(path: str) -> Tuple[int, int, int]:
+    return tuple(int(v) for v in read_nifti_header(path)["shape_xyz"][:3][::-1])
+
+
 @dataclasses.dataclass
 class Transform:
     """One case's drawn transform: ``L`` (3x3) and ``shift_frac`` (the shift as a fraction of
@@ -487,14 +646,20 @@ class Transform:
     bias: Tuple[float, ...]
     field: Optional[np.ndarray] = None
 
-    def affine(self, n_in, n_out) -> Tuple[np.ndarray, np.ndarray]:
+    def affine(self, n_in, n_out, alignment=None) -> Tuple[np.ndarray, np.ndarray]:
+        """``case_affine`` of this transform: with ``alignment`` = ``(ref_shape, (A, t))`` the
+        volume is placed through the reference file's grid and ``align_affine``."""
         n_out = tuple(int(v) for v in n_out)
-        return volume_affine(self.L, self.shift_frac * np.array(n_out, dtype=np.float64), n_in, n_out)
+        return case_affine(self.L, self.shift_frac * np.array(n_out, dtype=np.float64), n_in, n_out, alignment)
 
-    def affine12(self, n_in, n_out) -> Tuple[float, ...]:
+    def affine12(self, n_in, n_out, alignment=None) -> Tuple[float, ...]:
         """``affine`` as the twelve doubles the C entry points take: row-major A, then t."""
-        A, t = self.affine(n_in, n_out)
-        return tuple(float(v) for v in A.reshape(-1)) + tuple(float(v) for v in t)
+        return affine12_of(*self.affine(n_in, n_out, alignment))
+
+    @staticmethod
+    def identity(n_modalities: int) -> "Transform":
+        """The transform of a case that is not augmented: ``affine`` is the plain resampler's map."""
+        return Transform(np.eye(3), np.zeros(3), (1.0,) * int(n_modalities), (0.0,) * int(n_modalities))
 
 
 def draw_transform(aug, seed: int, epoch: int, case_number: int,
@@ -920,7 +1085,7 @@ class ProstateDataset(Dataset):
     def __init__(self, data_dir: str, modalities: Optional[List[str]] = None, missing_strategy: str = "zero_fill",
                  target_size: Tuple[int, int, int] = (128, 128, 128), is_training: bool = True,
                  data_type: str = "BPH", device_resample: bool = False, augment=None, augment_seed: int = 0,
-                 patches=None):
+                 patches=None, align=None, corrections=None):
         """``augment`` (an ``Augment`` or a dict of its fields; None: off, every sample as
         before): each case is resampled under a transform drawn by ``draw_transform(augment,
         augment_seed, epoch, case index)``, one geometry for all its modalities and its label,
@@ -929,7 +1094,19 @@ class ProstateDataset(Dataset):
         before): patch training -- a sample is the case's P crops of the patch shape, cut from
         the case grid under that transform (the identity draw without ``augment``) at origins
         drawn by ``draw_patches`` / ``pick_origins``; ``target_size`` is unused, ``set_epoch``
-        moves the patch draws too, and an elastic ``augment`` is not supported with it."""
+        moves the patch draws too, and an elastic ``augment`` is not supported with it.
+        ``align`` (anything ``predict.Alignment.of`` accepts; None: off, every sample as before):
+        every volume of a case, the label included, is placed on the grid of the reference file
+        through its NIfTI world geometry (``case_affine``: the case grid scaled onto the
+        reference's native grid, then ``align_affine`` into the volume's file) instead of being
+        stretched onto it; a grid voxel outside a file's field of view reads 0.  The reference is
+        ``align.to``: ``"label"`` (the default: the label file, whose own map is then the
+        identity) or a modality name; with ``patches`` a ``grid`` of None is its shape.  It
+        composes with ``augment``, ``patches`` and ``device_resample``, and both kinds of loader
+        give the same batches.  ``corrections`` (``predict.register_dataset``'s dict ``{case_id:
+        {modality: six parameters}}`` or the path of its JSON; needs ``align``): the rigid
+        correction of each modality goes into its map.  Training never registers on the fly:
+        ``mode="register"`` without ``corrections`` raises."""
         if missing_strategy not in ("zero_fill", "skip", "duplicate"):
             raise ValueError(f"unsupported missing-modality strategy: {missing_strategy}")
         self.augment = Augment.of(augment)
@@ -937,6 +1114,20 @@ class ProstateDataset(Dataset):
         if self.patches is not None and self.augment is not None and self.augment.elastic:
             raise ValueError("patches and Augment.elastic_grid cannot be combined: the patch resampler has no "
                              "deforming form")
+        self.align = None
+        if align is not None:
+            from .predict import Alignment
+            self.align = Alignment.of(align)
+        if isinstance(corrections, (str, os.PathLike)):
+            import json
+            with open(corrections) as f:
+                corrections = json.load(f)
+        if corrections is not None and self.align is None:
+            raise ValueError("corrections need align: they are rigid corrections of the header alignment")
+        if self.align is not None and self.align.mode == "register" and corrections is None:
+            raise ValueError("training does not register on the fly: pass corrections=predict.register_dataset(...) "
+                             "(or its JSON file) with align mode 'register'")
+        self.corrections = corrections
         self.augment_seed = int(augment_seed)
         self.epoch = 0
         self.data_dir = data_dir
@@ -1003,6 +1194,29 @@ class ProstateDataset(Dataset):
             return a[0]
         raise ValueError(f"unsupported image dimensions: {a.shape}")
 
+    def _alignments(self, case: Dict) -> Optional[Dict]:
+        """``{modality: (ref_shape, (A, t)), ..., "label": ...}``: the ``alignment`` argument of
+        ``Transform.affine`` for every file of the case (``align_affine`` from the reference file,
+        with the modality's rigid correction about the centre of the fixed modality's file --
+        ``registration_fixed`` -- when ``corrections`` holds one); None without ``align``."""
+        if self.align is None:
+            return None
+        files = case["modality_files"]
+        to = self.align.to if self.align.to is not None else "label"
+        ref = case["label_path"] if to == "label" else files.get(to)
+        if ref is None:
+            raise FileNotFoundError(f"case {case['case_id']}: no file for the alignment reference {to!r}")
+        ref_geo, ref_shape = read_nifti_geometry(ref), _shape_zyx(ref)
+        corr = (self.corrections or {}).get(case["case_id"]) or {}
+        fixed = registration_fixed(self.modalities, files, to)
+        out = {"label": (ref_shape, align_affine(ref_geo, read_nifti_geometry(case["label_path"])))}
+        for m, p in files.items():
+            T = None
+            if corr.get(m) is not None and m != fixed:
+                T = rigid_correction(corr[m], read_nifti_geometry(files[fixed]), _shape_zyx(files[fixed]))
+            out[m] = (ref_shape, align_affine(ref_geo, read_nifti_geometry(p), T))
+        return out
+
     def set_epoch(self, epoch: int) -> None:
         """The epoch whose transforms and patch origins ``__getitem__`` draws (no effect without
         ``augment`` or ``patches``).
@@ -1011,24 +1225,29 @@ class ProstateDataset(Dataset):
         self.epoch = int(epoch)
 
     def _augmented(self, idx: int) -> Dict:
-        """``__getitem__`` under the case's drawn transform: every volume resampled by
+        """``__getitem__`` under the case's drawn transform (the identity one when only ``align``
+        is on), every volume placed by ``align`` when it is on: every volume resampled by
         ``resample_affine`` (also one already of the target shape), or -- ``device_resample`` --
         handed over undecoded with the twelve doubles and the gain / bias it is to be resampled
         with.  With ``elastic_grid`` on the case's control grid goes along: ``resample_deform``
         here, ``"field"`` in the handed-over dict there."""
         case = self.case_list[idx]
         files = case["modality_files"]
-        tf = draw_transform(self.augment, self.augment_seed, self.epoch, idx, len(self.modalities))
+        tf = Transform.identity(len(self.modalities)) if self.augment is None else \
+            draw_transform(self.augment, self.augment_seed, self.epoch, idx, len(self.modalities))
+        al = self._alignments(case)  # per modality and for "label": (ref_shape, (A, t)), or None
         if self.device_resample:
             raws = [read_nifti_raw(files[m]) if m in files else None for m in self.modalities]
             lab = read_nifti_raw(case["label_path"])
-            aug = {"affine": [None if r is None else tf.affine12(r.shape, self.target_size) for r in raws],
-                   "label_affine": tf.affine12(lab.shape, self.target_size), "gain": tf.gain, "bias": tf.bias}
-            if self.augment.elastic:  # a CPU tensor, so that the DataLoader's pin_memory handles it
+            aug = {"affine": [None if r is None else tf.affine12(r.shape, self.target_size, al and al[m])
+                              for m, r in zip(self.modalities, raws)],
+                   "label_affine": tf.affine12(lab.shape, self.target_size, al and al["label"]), "gain": tf.gain,
+                   "bias": tf.bias}
+            if tf.field is not None:  # a CPU tensor, so that the DataLoader's pin_memory handles it
                 aug["field"] = torch.from_numpy(np.ascontiguousarray(tf.field))
             return {"raw_images": raws, "raw_label": lab, "case_id": case["case_id"], "augment": aug}
-        def sample(vol, **kw):  # with an elastic field the same gather at the deformed positions
-            A, t = tf.affine(vol.shape, self.target_size)
+        def sample(vol, alignment, **kw):  # with an elastic field the same gather at the deformed positions
+            A, t = tf.affine(vol.shape, self.target_size, alignment)
             if tf.field is None:
                 return resample_affine(vol, self.target_size, A, t, **kw)
             return resample_deform(vol, self.target_size, A, t, tf.field, **kw)
@@ -1040,9 +1259,9 @@ class ProstateDataset(Dataset):
                 chans.append(np.zeros(self.target_size, dtype=np.float32))
                 continue
             vol = self._first_volume(read_nifti(p)).astype(np.float32)
-            chans.append(sample(vol, gain=tf.gain[c], bias=tf.bias[c]))
+            chans.append(sample(vol, al and al[m], gain=tf.gain[c], bias=tf.bias[c]))
         lab = self._first_volume(read_nifti(case["label_path"]))
-        label = (sample(lab, nearest=True) > 0).astype(np.float32)[None]
+        label = (sample(lab, al and al["label"], nearest=True) > 0).astype(np.float32)[None]
         return {"image": torch.from_numpy(np.stack(chans, 0)).float(), "label": torch.from_numpy(label),
                 "case_id": case["case_id"]}
 
@@ -1060,21 +1279,25 @@ class ProstateDataset(Dataset):
         ps = self.patches
         tf = draw_transform(self.augment if self.augment is not None else Augment(), self.augment_seed, self.epoch,
                             idx, len(self.modalities))
+        al = self._alignments(case)  # per modality and for "label": (ref_shape, (A, t)), or None
         if self.device_resample:
             raws = [read_nifti_raw(files[m]) if m in files else None for m in self.modalities]
             lab = read_nifti_raw(case["label_path"])
-            grid = ps.grid if ps.grid is not None else tuple(lab.shape)
+            grid = ps.grid if ps.grid is not None else tuple(lab.shape) if al is None else al["label"][0]
             rank_u, fallback = draw_patches(ps, ps.seed, self.epoch, idx, grid)
-            draws = {"affine": [None if r is None else tf.affine12(r.shape, grid) for r in raws],
-                     "label_affine": tf.affine12(lab.shape, grid), "gain": tf.gain, "bias": tf.bias, "grid": grid,
+            draws = {"affine": [None if r is None else tf.affine12(r.shape, grid, al and al[m])
+                                for m, r in zip(self.modalities, raws)],
+                     "label_affine": tf.affine12(lab.shape, grid, al and al["label"]), "gain": tf.gain,
+                     "bias": tf.bias, "grid": grid,
                      # CPU tensors, so that the DataLoader's pin_memory handles them
                      "rank_u": torch.from_numpy(rank_u), "fallback": torch.from_numpy(fallback)}
             return {"raw_images": raws, "raw_label": lab, "case_id": case["case_id"], "patches": draws}
         from .predict import Normalisation, gather_windows
         lab = self._first_volume(read_nifti(case["label_path"]))
-        grid = ps.grid if ps.grid is not None else tuple(lab.shape)
+        grid = ps.grid if ps.grid is not None else tuple(lab.shape) if al is None else al["label"][0]
         rank_u, fallback = draw_patches(ps, ps.seed, self.epoch, idx, grid)
-        label_grid = (resample_affine(lab, grid, *tf.affine(lab.shape, grid), nearest=True) > 0).astype(np.float32)
+        label_grid = (resample_affine(lab, grid, *tf.affine(lab.shape, grid, al and al["label"]), nearest=True)
+                      > 0).astype(np.float32)
         origins, count = pick_origins(label_grid, ps.patch_size, rank_u, fallback)
         P = ps.patches_per_case
         image = np.zeros((P, len(self.modalities)) + ps.patch_size, dtype=np.float32)
@@ -1085,7 +1308,7 @@ class ProstateDataset(Dataset):
             vol = self._first_volume(read_nifti(p)).astype(np.float32)
             if ps.normalise:  # once per volume, not per patch
                 vol = Normalisation.of(ps.normalise).apply(vol)
-            A, t = tf.affine(vol.shape, grid)
+            A, t = tf.affine(vol.shape, grid, al and al[m])
             for k in range(P):
                 image[k, c] = _resample_patch(vol, grid, A, t, origins[k], ps.patch_size, tf.gain[c], tf.bias[c])
         label = gather_windows(label_grid[None], origins, ps.patch_size)
@@ -1096,7 +1319,7 @@ class ProstateDataset(Dataset):
     def __getitem__(self, idx: int) -> Dict:
         if self.patches is not None:
             return self._patched(idx)
-        if self.augment is not None:
+        if self.augment is not None or self.align is not None:
             return self._augmented(idx)
         case = self.case_list[idx]
         if self.device_resample:
@@ -1126,7 +1349,7 @@ def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, mod
                    missing_strategy: str = "zero_fill", target_size=(128, 128, 128), num_workers: int = 0,
                    is_training: bool = True, data_type: str = "BPH", indices=None, rank: int = 0,
                    world_size: int = 1, device_resample: bool = False, augment=None,
-                   augment_seed: int = 0, patches=None) -> DataLoader:
+                   augment_seed: int = 0, patches=None, align=None, corrections=None) -> DataLoader:
     """script/data_loader.py:421-466 (pinned host batches; Trainer stages them to the GPU on
     a copy stream one batch ahead).  ``world_size > 1``: each rank iterates its own
     DistributedSampler shard (call ``loader.sampler.set_epoch(epoch)`` every epoch).
@@ -1139,12 +1362,14 @@ def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, mod
     of its ``batch_size`` cases, ``image`` (batch_size * P, M, wd, wh, ww), ``label``
     (batch_size * P, 1, ...), ``case_id`` repeated P times, plus ``picks`` (batch_size, 3P + 1):
     the origins and the foreground count per case; ``target_size`` is unused.  Both kinds of
-    loader give equal batches here too (``assemble_patch_batch``)."""
+    loader give equal batches here too (``assemble_patch_batch``).
+    ``align`` / ``corrections``: the volumes are placed by their world geometry
+    (``ProstateDataset``); both kinds of loader give equal batches with it as well."""
     patches = PatchSampling.of(patches)
     ds = ProstateDataset(data_dir, modalities=modalities, missing_strategy=missing_strategy,
                          target_size=target_size, is_training=is_training, data_type=data_type,
                          device_resample=device_resample, augment=augment, augment_seed=augment_seed,
-                         patches=patches)
+                         patches=patches, align=align, corrections=corrections)
     collate = _CollateRaw(target_size, patches) if device_resample else None
     if patches is not None and not device_resample:
         collate = _collate_patches

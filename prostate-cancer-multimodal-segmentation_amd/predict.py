@@ -45,6 +45,14 @@ the host forms of a robust window -- two exact order statistics of a volume, the
 them and scaled to [0, 1]; ``Normalisation`` names the choice wherever ``normalise`` is taken
 (``True`` stays min-max); on the device pcms_volume_window selects the window from the raw bytes
 and the ``_window`` resampling kernels consume it, bit for bit.
+
+Modality alignment: ``Alignment`` names how the modalities of a case reach one grid --
+through their NIfTI world geometry (``data.world_matrix`` / ``align_affine`` / ``case_affine``) and
+optionally a rigid registration; ``joint_histogram`` / ``normalised_mutual_information`` /
+``register_rigid`` are the host forms of the similarity and of the search that maximises it;
+``joint_histogram_device`` (pcms_joint_histogram, on the counts) / ``register_rigid_device`` /
+``register_case_device`` / ``register_dataset`` run them on the GPU; ``prepare_case``,
+``prepare_case_device`` and ``predict_case`` take ``align=``.
 """
 from __future__ import annotations
 
@@ -243,9 +251,11 @@ def _case_files(case_dir: str) -> List[Optional[str]]:
     return paths
 
 
-def _case_plan(case_dir: str, target_size, handle_missing: str):
+def _case_plan(case_dir: str, target_size, handle_missing: str, align=None):
     """(paths, the grid every channel is formed on, the channel a missing modality copies or
-    None for zeros): what ``prepare_case`` and ``prepare_case_device`` decide alike."""
+    None for zeros): what ``prepare_case`` and ``prepare_case_device`` decide alike.  With
+    ``align`` (an ``Alignment``) ``target_size=None`` is the native grid of the reference file and
+    the modalities' shapes may differ."""
     if handle_missing not in ("zero_fill", "skip", "duplicate"):
         raise ValueError(f"unsupported missing-modality strategy: {handle_missing}")
     paths = _case_files(case_dir)
@@ -255,6 +265,8 @@ def _case_plan(case_dir: str, target_size, handle_missing: str):
         raise FileNotFoundError(f"no .nii file for {missing} in {case_dir}")
     if target_size is not None:
         grid = tuple(int(v) for v in target_size)
+    elif align is not None:
+        grid = _shape_of(_case_reference(paths, align))
     else:
         shapes = {p: tuple(read_nifti_header(p)["shape_xyz"][:3][::-1]) for p in paths if p is not None}
         if len(set(shapes.values())) != 1:
@@ -269,8 +281,427 @@ def _first_volume(a: np.ndarray) -> np.ndarray:
     return a if a.ndim == 3 else a[0]
 
 
+# ---- modality alignment ------------------------------------------------------------
+# Geometry lives in data.py (world_matrix, align_affine, case_affine).  Below: the similarity of two
+# volumes of different contrast -- the joint histogram of their window-normalised intensities under
+# an affine and its normalised mutual information -- and a rigid registration that maximises it.
+# The host forms define what csrc/align.hip counts, exactly.
+DEFAULT_LEVELS = (((1, 2, 2), (4.0, 2.0, 1.0)), ((1, 1, 1), (0.5, 0.25)))
+
+
+def _bin_index(v: np.ndarray, bins: int) -> np.ndarray:
+    """``fl32(v * float32(bins))`` clamped to ``[0, bins - 1]`` as a float and truncated: for ``v``
+    in [0, 1] that is ``min(int(fl32(v * bins)), bins - 1)``; NaNs (never counted) map to 0."""
+    with np.errstate(over="ignore", invalid="ignore"):
+        b = np.asarray(v, dtype=np.float32) * np.float32(bins)
+        b = np.where(b < 0, np.float32(0), np.where(b > np.float32(bins - 1), np.float32(bins - 1), b))
+    return np.where(np.isnan(b), np.float32(0), b).astype(np.int64)
+
+
+def _check_hist_args(bins, stride) -> Tuple[int, Tuple[int, int, int]]:
+    if isinstance(bins, bool) or int(bins) != bins or not 2 <= int(bins) <= 64:
+        raise ValueError(f"bins is an integer in 2..64, got {bins!r}")
+    stride = _data._axes3(stride, "stride")
+    if min(stride) < 1:
+        raise ValueError(f"every stride is at least 1, got {stride}")
+    return int(bins), stride
+
+
+def joint_histogram(fix: np.ndarray, mov: np.ndarray, A, t, fix_lohi, mov_lohi, bins: int = 32,
+                    stride: Sequence[int] = (1, 1, 1)) -> np.ndarray:
+    """The joint intensity histogram of a fixed and a moving (D, H, W) volume under the affine
+    ``(A, t)`` (fixed array index -> moving array index), int64 ``(bins, bins)``.  For every
+    lattice index ``q = (a*sd, b*sh, e*sw)`` inside the fixed volume: ``f`` is
+    ``normalise_window(fix, fix_lohi)`` at ``q``; ``m`` is the linear sample
+    (``data.resample_affine``'s gather) of ``normalise_window(mov, mov_lohi)`` at
+    ``c_a = ((A[a][0]*q_d + A[a][1]*q_h) + A[a][2]*q_w) + t[a]``.  The voxel counts only if
+    ``-0.5 <= c_a < n_a - 0.5`` on all three moving axes and neither value is NaN; then
+    ``hist[bin(f), bin(m)] += 1`` with ``bin(v) = min(int(fl32(v * float32(bins))), bins - 1)``
+    (``_bin_index``).  The sum of the table is the overlap count.  libpcms_hip's
+    pcms_joint_histogram is compared with this on the counts."""
+    bins, stride = _check_hist_args(bins, stride)
+    A = np.asarray(A, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    fix, mov = _volume(fix), _volume(mov)
+    f = normalise_window(fix, fix_lohi)[::stride[0], ::stride[1], ::stride[2]]
+    mv = normalise_window(mov, mov_lohi)
+    shapes = ((-1, 1, 1), (1, -1, 1), (1, 1, -1))
+    q = [np.arange(0, n, s, dtype=np.int64).astype(np.float64).reshape(sh)
+         for n, s, sh in zip(fix.shape, stride, shapes)]
+    with np.errstate(over="ignore", invalid="ignore"):
+        c = [((A[a, 0] * q[0] + A[a, 1] * q[1]) + A[a, 2] * q[2]) + t[a] for a in range(3)]
+        inside = np.ones(f.shape, dtype=bool)
+        for a in range(3):
+            inside = inside & ((c[a] >= -0.5) & (c[a] < mov.shape[a] - 0.5))
+    with np.errstate(over="ignore", invalid="ignore"):
+        m = _data._sample_at(mv, c, False, 1.0, 0.0)
+    ok = inside & ~np.isnan(f) & ~np.isnan(m)
+    flat = _bin_index(f, bins)[ok] * bins + _bin_index(m, bins)[ok]
+    return np.bincount(flat, minlength=bins * bins).astype(np.int64).reshape(bins, bins)
+
+
+def normalised_mutual_information(hist) -> float:
+    """``(H(X) + H(Y)) / H(X, Y)`` of a joint count table, in fp64 from the counts: with
+    ``p = hist / N`` the entropies are ``-sum p log p`` over the non-empty cells of the table and
+    of its row and column sums.  1.0 for independent intensities, 2.0 for a one-to-one relation;
+    0.0 for an empty table and for a table with a single non-empty cell (``H(X, Y) = 0``: two
+    constant images say nothing about their alignment)."""
+    h = np.asarray(hist, dtype=np.float64)
+    n = float(h.sum())
+    if n <= 0.0:
+        return 0.0
+
+    def entropy(counts):
+        p = counts[counts > 0] / n
+        return float(-(p * np.log(p)).sum())
+
+    hxy = entropy(h.reshape(-1))
+    if hxy <= 0.0:
+        return 0.0
+    return (entropy(h.sum(axis=1)) + entropy(h.sum(axis=0))) / hxy
+
+
+@dataclasses.dataclass
+class Alignment:
+    """How the modalities of a case are brought onto one grid.  ``mode``: ``"world"`` -- every file
+    is resampled through its header geometry (``data.align_affine``) onto the reference file's
+    grid -- or ``"register"`` -- each other modality is first registered rigidly to the reference
+    (``register_rigid``) and the correction goes into its affine.  ``to``: the reference, a modality
+    name or a file path (None: the caller's default; training also takes ``"label"``).  ``bins``,
+    ``levels``, ``min_overlap``, ``max_translation_mm`` and ``max_rotation_deg`` are
+    ``register_rigid``'s."""
+    mode: str = "world"
+    to: Optional[str] = None
+    bins: int = 32
+    levels: tuple = DEFAULT_LEVELS
+    min_overlap: float = 0.5
+    max_translation_mm: float = 20.0
+    max_rotation_deg: float = 10.0
+
+    MODES = ("world", "register")
+
+    @staticmethod
+    def of(x) -> Optional["Alignment"]:
+        """``None``: no alignment (None); a mode name, a dict of the fields or an instance."""
+        if x is None or isinstance(x, Alignment):
+            return x
+        if isinstance(x, str):
+            return Alignment(mode=x)
+        if isinstance(x, dict):
+            return Alignment(**x)
+        raise ValueError(f"align is None, a mode name, a dict or an Alignment, got {x!r}")
+
+    def __post_init__(self):
+        if self.mode not in self.MODES:
+            raise ValueError(f"unknown alignment mode {self.mode!r}: one of {self.MODES}")
+        if self.to is not None and not isinstance(self.to, str):
+            raise ValueError(f"Alignment.to is None, a modality name or a file path, got {self.to!r}")
+        self.bins = _check_hist_args(self.bins, (1, 1, 1))[0]
+        levels = []
+        for level in self.levels:
+            stride, steps = level
+            steps = tuple(float(s) for s in steps)
+            if not steps or not all(math.isfinite(s) and s > 0.0 for s in steps):
+                raise ValueError(f"the steps of a level are finite numbers > 0, got {level!r}")
+            levels.append((_check_hist_args(2, stride)[1], steps))
+        if not levels:
+            raise ValueError("Alignment.levels holds at least one (stride, steps) level")
+        self.levels = tuple(levels)
+        self.min_overlap = float(self.min_overlap)
+        self.max_translation_mm, self.max_rotation_deg = float(self.max_translation_mm), float(self.max_rotation_deg)
+        if not 0.0 <= self.min_overlap <= 1.0 or not self.max_translation_mm >= 0.0 or not self.max_rotation_deg >= 0.0:
+            raise ValueError("Alignment: min_overlap lies in [0, 1] and the two limits are not negative")
+
+
+def _host_lohi(vol: np.ndarray, norm: Optional[Normalisation]) -> np.ndarray:
+    """The (lo, hi) window a volume's histogram values are normalised with: ``norm``'s percentile
+    window, or the minimum and maximum (also when ``norm`` is None)."""
+    if norm is not None and norm.method == "percentile":
+        return intensity_window(vol, norm.lower, norm.upper, norm.above)
+    v = np.asarray(vol).astype(np.float32)
+    return np.array([v.min(), v.max()], dtype=np.float32)
+
+
+def _pattern_search(evaluate, fix_shape, fix_geometry: dict, mov_geometry: dict, settings: Alignment) -> dict:
+    """``register_rigid``'s search over an evaluator ``evaluate(A, t, stride) -> (bins, bins)``
+    counts: the host and the device form differ in that evaluator alone."""
+    centre = _data.world_centre(fix_geometry, fix_shape)
+    seen, count = {}, [0]
+
+    def score(params, stride):
+        """NMI of ``params`` on the lattice of ``stride``, or None below the overlap floor."""
+        key = (tuple(params), stride)
+        if key not in seen:
+            A, t = _data.align_affine(fix_geometry, mov_geometry, _data.rigid_world(params, centre))
+            hist = np.asarray(evaluate(A, t, stride))
+            count[0] += 1
+            lattice = int(np.prod([-(-n // s) for n, s in zip(fix_shape, stride)]))
+            seen[key] = normalised_mutual_information(hist) if int(hist.sum()) >= settings.min_overlap * lattice \
+                else None
+        return seen[key]
+
+    def allowed(params):
+        return all(abs(v) <= settings.max_translation_mm for v in params[:3]) and \
+            all(abs(v) <= settings.max_rotation_deg for v in params[3:])
+
+    params = [0.0] * 6
+    fine = settings.levels[-1][0]
+    before = score(params, fine)
+    for stride, steps in settings.levels:
+        best = score(params, stride)
+        for step in steps:
+            improved = True
+            while improved:
+                improved = False
+                for k in range(6):
+                    for sign in (1.0, -1.0):
+                        cand = list(params)
+                        cand[k] = cand[k] + sign * step
+                        if not allowed(cand):
+                            continue
+                        s = score(cand, stride)
+                        if s is not None and (best is None or s > best):
+                            params, best, improved = cand, s, True
+                            break
+    after = score(params, fine)
+    return {"params": tuple(float(v) for v in params), "before": 0.0 if before is None else before,
+            "after": 0.0 if after is None else after, "evaluations": count[0]}
+
+
+def register_rigid(fix: np.ndarray, mov: np.ndarray, fix_geometry: dict, mov_geometry: dict, fix_lohi=None,
+                   mov_lohi=None, normalise=None, settings=None) -> dict:
+    """Rigid registration of a moving volume to a fixed volume of another contrast, both (z, y, x)
+    arrays with their ``read_nifti_geometry`` dicts.  Six parameters ``(tz, ty, tx mm; rz, ry, rx
+    degrees)`` describe a rigid motion in world millimetres about the fixed volume's centre
+    (``data.rigid_world``); it is the ``correction`` of ``data.align_affine(fix_geometry,
+    mov_geometry, .)``, whose ``(A, t)`` the similarity ``normalised_mutual_information(
+    joint_histogram(fix, mov, A, t, fix_lohi, mov_lohi, bins, stride))`` is evaluated under.
+    A deterministic coordinate pattern search maximises it.  ``settings`` (an ``Alignment``, a
+    dict of its fields or None for the defaults) holds ``bins``, the limits and ``levels``: per level a
+    lattice stride and a list of step sizes, equal in mm and in degrees.  For each step the six
+    parameters are swept in order; ``+step`` is tried, then ``-step``, the first strict improvement
+    is accepted and the sweep moves to the next parameter; the sweep repeats until none improves.
+    A candidate is rejected without comparison when its overlap count is below ``min_overlap`` of
+    the lattice size, or when a translation exceeds ``max_translation_mm`` or a rotation
+    ``max_rotation_deg`` in absolute value.  A point met twice is evaluated once.
+    ``fix_lohi`` / ``mov_lohi``: the windows of the histogram (None: from ``normalise`` --
+    the percentile window it names, else the minimum and maximum).
+    Returns ``{"params": six floats, "before": the similarity at zero, "after": the similarity at
+    the result (both on the last level's lattice; 0.0 below the overlap floor), "evaluations":
+    the number of histograms formed}``."""
+    settings = Alignment.of(settings) or Alignment()
+    norm = Normalisation.of(normalise)
+    fix, mov = _volume(fix), _volume(mov)
+    fl = _host_lohi(fix, norm) if fix_lohi is None else np.asarray(fix_lohi, dtype=np.float32)
+    ml = _host_lohi(mov, norm) if mov_lohi is None else np.asarray(mov_lohi, dtype=np.float32)
+    return _pattern_search(lambda A, t, stride: joint_histogram(fix, mov, A, t, fl, ml, settings.bins, stride),
+                           fix.shape, fix_geometry, mov_geometry, settings)
+
+
+def _device_raw(raw, what: str):
+    if not isinstance(raw, _data.RawVolume) or raw.data.device.type != "cuda":
+        raise RuntimeError(f"{what} needs RawVolumes whose bytes are on a GPU (RawVolume.to(device)): pcms_amd has no "
+                           "CPU fallback -- use the host form of the same name without _device")
+    itemsize = np.dtype(_data._NIFTI_DTYPES[raw.code]).itemsize
+    if raw.data.dtype != torch.uint8 or not raw.data.is_contiguous() or \
+            raw.data.numel() != int(np.prod(raw.shape)) * itemsize:
+        raise ValueError(f"RawVolume.data must be the {int(np.prod(raw.shape)) * itemsize} contiguous bytes of shape "
+                         f"{raw.shape}, datatype {raw.code}")
+    return raw
+
+
+def _device_lohi(lohi, device) -> torch.Tensor:
+    if isinstance(lohi, torch.Tensor):
+        if lohi.device != device or lohi.dtype != torch.float32 or lohi.numel() != 2 or not lohi.is_contiguous():
+            raise ValueError(f"a window is two contiguous fp32 values on {device}")
+        return lohi
+    return torch.from_numpy(np.asarray(lohi, dtype=np.float32).reshape(2).copy()).to(device)
+
+
+def _joint_enqueue(fix_raw, mov_raw, A, t, fix_lohi: torch.Tensor, mov_lohi: torch.Tensor, bins: int, stride,
+                   work: torch.Tensor) -> torch.Tensor:
+    """The int32 (bins, bins) table with pcms_joint_histogram enqueued on the current stream."""
+    from ._lib import call
+    host = (ctypes.c_double * 12)(*_data.affine12_of(A, t))  # read during the call (kernel arguments)
+    hist = torch.empty((bins, bins), dtype=torch.int32, device=fix_raw.data.device)
+    call("pcms_joint_histogram", fix_raw.data, int(fix_raw.code), *fix_raw.shape, float(fix_raw.slope),
+         float(fix_raw.inter), fix_lohi, mov_raw.data, int(mov_raw.code), *mov_raw.shape, float(mov_raw.slope),
+         float(mov_raw.inter), mov_lohi, ctypes.addressof(host), *stride, bins, hist, work)
+    return hist
+
+
+def _joint_work(bins: int, device) -> torch.Tensor:
+    from ._lib import query
+    return torch.empty(query("pcms_joint_histogram_work_bytes", bins) // 4, dtype=torch.int32, device=device)
+
+
+def joint_histogram_device(fix_raw, mov_raw, A, t, fix_lohi, mov_lohi, bins: int = 32,
+                           stride: Sequence[int] = (1, 1, 1)) -> torch.Tensor:
+    """``joint_histogram`` on the GPU, on the counts exactly (pcms_joint_histogram): two
+    ``RawVolume``s whose bytes are on one GPU in, a ``torch.int64`` (bins, bins) tensor there out,
+    enqueued on the current stream.  ``fix_lohi`` / ``mov_lohi``: two fp32 values each, as device
+    tensors (pcms_volume_minmax's or pcms_volume_window's, consumed where they are) or as host
+    numbers (uploaded).  Host bytes raise; ValueError for what the entry point rejects."""
+    bins, stride = _check_hist_args(bins, stride)
+    fix_raw, mov_raw = _device_raw(fix_raw, "joint_histogram_device"), _device_raw(mov_raw, "joint_histogram_device")
+    device = fix_raw.data.device
+    if mov_raw.data.device != device:
+        raise ValueError(f"the two volumes are on different devices: {device} and {mov_raw.data.device}")
+    A = np.asarray(A, dtype=np.float64).reshape(3, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(3)
+    if not (np.isfinite(A).all() and np.isfinite(t).all()):
+        raise ValueError("the affine must be finite")
+    with torch.cuda.device(device):
+        hist = _joint_enqueue(fix_raw, mov_raw, A, t, _device_lohi(fix_lohi, device), _device_lohi(mov_lohi, device),
+                              bins, stride, _joint_work(bins, device))
+        return hist.to(torch.int64)
+
+
+def _window_device(raw, norm: Optional[Normalisation]) -> torch.Tensor:
+    """``_host_lohi`` on the device: two fp32 values from pcms_volume_window or pcms_volume_minmax."""
+    lohi = torch.empty(2, dtype=torch.float32, device=raw.data.device)
+    _lohi_enqueue(raw, norm if norm is not None and norm.method == "percentile" else Normalisation(), lohi)
+    return lohi
+
+
+def register_rigid_device(fix_raw, mov_raw, fix_geometry: dict, mov_geometry: dict, fix_lohi=None, mov_lohi=None,
+                          normalise=None, settings=None) -> dict:
+    """``register_rigid`` with pcms_joint_histogram as its evaluator: the same Python search, one
+    small table read back per evaluation.  The counts are the host form's, so the search takes the
+    same path and returns the same parameters, similarities and evaluation count exactly.
+    ``fix_raw`` / ``mov_raw``: ``RawVolume``s whose bytes are on one GPU; the windows default to
+    pcms_volume_window (a percentile ``normalise``) or pcms_volume_minmax."""
+    settings = Alignment.of(settings) or Alignment()
+    norm = Normalisation.of(normalise)
+    fix_raw, mov_raw = _device_raw(fix_raw, "register_rigid_device"), _device_raw(mov_raw, "register_rigid_device")
+    device = fix_raw.data.device
+    if mov_raw.data.device != device:
+        raise ValueError(f"the two volumes are on different devices: {device} and {mov_raw.data.device}")
+    with torch.cuda.device(device):
+        fl = _window_device(fix_raw, norm) if fix_lohi is None else _device_lohi(fix_lohi, device)
+        ml = _window_device(mov_raw, norm) if mov_lohi is None else _device_lohi(mov_lohi, device)
+        work = _joint_work(settings.bins, device)  # one workspace: the evaluations are ordered on the stream
+
+        def evaluate(A, t, stride):
+            return _joint_enqueue(fix_raw, mov_raw, A, t, fl, ml, settings.bins, stride, work).cpu().numpy()
+
+        return _pattern_search(evaluate, tuple(fix_raw.shape), fix_geometry, mov_geometry, settings)
+
+
+def _shape_of(path: str) -> Tuple[int, int, int]:
+    return tuple(int(v) for v in read_nifti_header(path)["shape_xyz"][:3][::-1])
+
+
+def _case_reference(paths: List[Optional[str]], align: Alignment) -> str:
+    """The file whose grid an aligned case is formed on: ``align.to`` as a modality name (its file
+    must be present) or a file path, else the first present modality's file."""
+    if align.to is None:
+        return next(p for p in paths if p is not None)
+    if align.to in MODALITIES:
+        p = paths[MODALITIES.index(align.to)]
+        if p is None:
+            raise FileNotFoundError(f"the reference modality {align.to!r} has no .nii file")
+        return p
+    if not os.path.exists(align.to):
+        raise FileNotFoundError(f"Alignment.to is neither a modality of {MODALITIES} nor a file: {align.to!r}")
+    return align.to
+
+
+def _fixed_modality(paths: List[Optional[str]], align: Alignment) -> int:
+    """The channel the other modalities are registered to: ``align.to`` when it names a present
+    modality, else the first present one (a label or another file only lends its grid)."""
+    present = [m for m, p in zip(MODALITIES, paths) if p is not None]
+    return MODALITIES.index(_data.registration_fixed(MODALITIES, present, align.to))
+
+
+def _aligned_affines(paths, grid, reference: str, corrections: Optional[dict], fixed: int):
+    """Per present channel the ``(A, t)`` of ``data.case_affine`` from ``grid`` through the
+    reference file's geometry into the channel's file, with its rigid correction (six parameters
+    about the centre of channel ``fixed``'s file) when it has one."""
+    ref_geo, ref_shape = _data.read_nifti_geometry(reference), _shape_of(reference)
+    out = {}
+    for c, p in enumerate(paths):
+        if p is None:
+            continue
+        T = None
+        if corrections is not None and corrections.get(MODALITIES[c]) is not None and c != fixed:
+            T = _data.rigid_correction(corrections[MODALITIES[c]]["params"], _data.read_nifti_geometry(paths[fixed]),
+                                       _shape_of(paths[fixed]))
+        pair = _data.align_affine(ref_geo, _data.read_nifti_geometry(p), T)
+        out[c] = _data.case_affine(np.eye(3), np.zeros(3), _shape_of(p), grid, (ref_shape, pair))
+    return out
+
+
+def register_case(case_dir_or_files, normalise=True, align="register") -> dict:
+    """The host form of ``register_case_device``: ``register_rigid`` of every other present
+    modality to the fixed one, ``{modality: result}``."""
+    paths, settings = _register_inputs(case_dir_or_files, align)
+    fixed = _fixed_modality(paths, settings)
+    fix = _first_volume(read_nifti(paths[fixed]))
+    geo = _data.read_nifti_geometry(paths[fixed])
+    return {MODALITIES[c]: register_rigid(fix, _first_volume(read_nifti(p)), geo, _data.read_nifti_geometry(p),
+                                          normalise=normalise, settings=settings)
+            for c, p in enumerate(paths) if p is not None and c != fixed}
+
+
+def _register_inputs(case_dir_or_files, align):
+    settings = Alignment.of(align) or Alignment(mode="register")
+    if isinstance(case_dir_or_files, dict):
+        unknown = [m for m in case_dir_or_files if m not in MODALITIES]
+        if unknown:
+            raise ValueError(f"unknown modalities {unknown}: the files are keyed by {MODALITIES}")
+        paths = [case_dir_or_files.get(m) for m in MODALITIES]
+    else:
+        paths = _case_files(case_dir_or_files)
+    if all(p is None for p in paths):
+        raise FileNotFoundError(f"no modality file in {case_dir_or_files!r}")
+    return paths, settings
+
+
+def register_case_device(case_dir_or_files, normalise=True, align="register", device="cuda", raws=None) -> dict:
+    """Rigid registration of a case's modalities on the GPU: ``{modality: register_rigid_device's
+    result}`` for every present modality but the fixed one -- ``align.to`` when it names a present
+    modality, else the first present one.  ``case_dir_or_files``: a case directory
+    (``<dir>/<modality>/*.nii``) or a ``{modality: path}`` dict.  The windows follow ``normalise``
+    (min-max when it is off).  Each file's bytes go up once (``raws``: channels already there)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"register_case_device needs a GPU, not '{device}': pcms_amd has no CPU fallback -- "
+                           "use predict.register_case on the host")
+    paths, settings = _register_inputs(case_dir_or_files, align)
+    norm = Normalisation.of(normalise)
+    fixed = _fixed_modality(paths, settings)
+    raws = dict(raws or {})
+    with torch.cuda.device(device):
+        for c, p in enumerate(paths):
+            if p is not None and c not in raws:
+                raws[c] = _data.read_nifti_raw(p).to(device)
+        geo = _data.read_nifti_geometry(paths[fixed])
+        fl = _window_device(raws[fixed], norm)
+        return {MODALITIES[c]: register_rigid_device(raws[fixed], raws[c], geo, _data.read_nifti_geometry(p),
+                                                     fix_lohi=fl, normalise=norm, settings=settings)
+                for c, p in enumerate(paths) if p is not None and c != fixed}
+
+
+def register_dataset(dataset, device="cuda", normalise=True, align="register") -> dict:
+    """``{case_id: {modality: [tz, ty, tx, rz, ry, rx]}}`` for every case of a ``ProstateDataset``
+    (or a ``Subset`` of one): ``register_case_device`` of the case's files, JSON-serialisable --
+    the ``corrections`` a dataset takes.  Produce it with the ``to`` the dataset will align with:
+    the fixed modality is chosen from it (``"label"`` or None: the first present modality)."""
+    base = getattr(dataset, "dataset", dataset)
+    indices = getattr(dataset, "indices", range(len(base.case_list)))
+    out = {}
+    for i in indices:
+        case = base.case_list[i]
+        files = {m: p for m, p in case["modality_files"].items() if m in MODALITIES}
+        res = register_case_device(files, normalise, align, device)
+        out[case["case_id"]] = {m: [float(v) for v in r["params"]] for m, r in res.items()}
+    return out
+
+
 def prepare_case(case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
-                 handle_missing: str = "zero_fill", normalise=True) -> np.ndarray:
+                 handle_missing: str = "zero_fill", normalise=True, align=None,
+                 return_alignment: bool = False) -> np.ndarray:
     """The five modalities of a case on one grid, (5, D, H, W) float32: per modality the first
     ``.nii`` in sorted order (volume 0 of a 4-D file), ``normalise``d when asked, else as fp32,
     then ``data.resample(., target_size)`` (linear).  A missing modality is zeros
@@ -279,19 +710,53 @@ def prepare_case(case_dir: str, target_size: Optional[Sequence[int]] = (128, 128
     With ``normalise=False`` a channel is the one the default training loader forms for the
     file; with ``normalise=True`` it is ``load_multimodal_images``' channel on the grid.
     ``normalise`` is anything ``Normalisation.of`` accepts: ``"percentile"`` (or a dict / a
-    ``Normalisation``) clips every modality to its own percentile window first."""
+    ``Normalisation``) clips every modality to its own percentile window first.
+    ``align`` (anything ``Alignment.of`` accepts; None: everything above, unchanged): every present
+    modality is resampled by ``data.resample_affine`` under ``data.case_affine`` -- the grid scaled
+    onto the reference file's native grid, then ``data.align_affine`` into the modality's file -- so
+    the channels show one place in space whatever each file's field of view, spacing and
+    orientation; a grid voxel outside a file's field of view reads 0.  The reference is
+    ``align.to`` (a modality name or a file path; default: the first present modality's file) and
+    ``target_size=None`` is its native grid; the modalities' shapes may differ.  ``"register"``
+    first registers every other modality to the fixed one (``register_case``) and puts the
+    correction into its affine.  ``return_alignment=True`` returns ``(channels, alignment)``, the
+    second as ``CasePrediction.alignment`` carries it."""
     norm = Normalisation.of(normalise)
-    paths, grid, dup = _case_plan(case_dir, target_size, handle_missing)
+    align = Alignment.of(align)
+    paths, grid, dup = _case_plan(case_dir, target_size, handle_missing, align)
+    affines, report = None, None
+    if align is not None:
+        fixed = _fixed_modality(paths, align)
+        if align.mode == "register":
+            report = register_case(dict(zip(MODALITIES, paths)), normalise, align)
+        affines = _aligned_affines(paths, grid, _case_reference(paths, align), report, fixed)
     chans: List[Optional[np.ndarray]] = []
-    for p in paths:
+    for c, p in enumerate(paths):
         if p is None:
             chans.append(None)
             continue
         vol = _first_volume(read_nifti(p))
         vol = norm.apply(vol) if norm is not None else vol.astype(np.float32)
-        chans.append(_data.resample(vol, grid))
+        chans.append(_data.resample(vol, grid) if affines is None else _data.resample_affine(vol, grid, *affines[c]))
     fill = np.zeros(grid, dtype=np.float32) if dup is None else chans[dup]
-    return np.stack([fill if c is None else c for c in chans], axis=0)
+    x = np.stack([fill if c is None else c for c in chans], axis=0)
+    return (x, _alignment_report(paths, align, report)) if return_alignment else x
+
+
+def _alignment_report(paths, align: Optional["Alignment"], report: Optional[dict]) -> Optional[dict]:
+    """``CasePrediction.alignment``: per present modality the six parameters and the similarity
+    before and after (zeros and None for header alignment alone and for the fixed modality);
+    None without ``align``."""
+    if align is None:
+        return None
+    out = {}
+    for m, p in zip(MODALITIES, paths):
+        if p is None:
+            continue
+        r = (report or {}).get(m)
+        out[m] = {"params": (0.0,) * 6, "before": None, "after": None} if r is None else \
+            {"params": r["params"], "before": r["before"], "after": r["after"]}
+    return out
 
 
 def tta_mean(probs: Sequence[np.ndarray], flips: Sequence[Tuple[int, ...]]) -> np.ndarray:
@@ -1324,27 +1789,51 @@ def sliding_window_device(predict_fn, x: torch.Tensor, window: Sequence[int], ov
 
 def prepare_case_device(case_dir: str, target_size: Optional[Sequence[int]] = (128, 128, 128),
                         handle_missing: str = "zero_fill", normalise=True,
-                        device="cuda") -> torch.Tensor:
+                        device="cuda", align=None, return_alignment: bool = False) -> torch.Tensor:
     """``prepare_case`` on the GPU, bit for bit, as the (1, 5, D, H, W) fp32 network input: each
     file's undecoded bytes (``data.read_nifti_raw``) go up once; pcms_volume_minmax and
     pcms_resample_linear_norm form the min-max normalised channel, pcms_volume_window and
     pcms_resample_linear_window the percentile one (the window is computed once per volume and
     read from device memory), ``data.resample_device`` the plain one.  Everything is enqueued on
-    the current stream."""
+    the current stream.
+    ``align``: ``prepare_case``'s, bit for bit too.  Per present modality one launch under the
+    twelve doubles of ``data.case_affine`` -- the host form's own -- fills the channel:
+    pcms_patch_resample_linear / pcms_patch_resample_window with one patch at origin 0 that is the
+    whole grid (the normalised corners), or pcms_resample_affine_linear without normalisation.
+    ``"register"`` runs ``register_case_device`` on the uploaded bytes first (it reads one small
+    table back per evaluation).  ``align=None``: nothing new is launched."""
     from ._lib import call
     norm = Normalisation.of(normalise)
+    align = Alignment.of(align)
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError(f"prepare_case_device needs a GPU, not '{device}': pcms_amd has no CPU fallback -- "
                            "use predict.prepare_case on the host")
-    paths, grid, dup = _case_plan(case_dir, target_size, handle_missing)
+    paths, grid, dup = _case_plan(case_dir, target_size, handle_missing, align)
+    report = None
     with torch.cuda.device(device):
         x = torch.empty((1, len(paths)) + grid, dtype=torch.float32, device=device)
         lohi = torch.empty(2, dtype=torch.float32, device=device)
-        for c, p in enumerate(paths):
-            if p is None:
+        raws = {c: _data.read_nifti_raw(p).to(device) for c, p in enumerate(paths) if p is not None}
+        affines = None
+        if align is not None:
+            if align.mode == "register":
+                report = register_case_device(dict(zip(MODALITIES, paths)), normalise, align, device, raws)
+            affines = _aligned_affines(paths, grid, _case_reference(paths, align), report,
+                                       _fixed_modality(paths, align))
+            origin = torch.zeros(3, dtype=torch.int32, device=device)
+        for c, raw in raws.items():
+            if affines is not None:
+                twelve = _data.affine12_of(*affines[c])
+                if norm is None:
+                    _data.resample_device(raw, grid, out=x[0, c], affine=twelve)
+                    continue
+                windowed = _lohi_enqueue(raw, norm, lohi) == "window"
+                host = (ctypes.c_double * 12)(*twelve)  # read during the call (kernel arguments)
+                call("pcms_patch_resample_window" if windowed else "pcms_patch_resample_linear", raw.data,
+                     int(raw.code), *raw.shape, float(raw.slope), float(raw.inter), ctypes.addressof(host), lohi, 1.0,
+                     0.0, *grid, origin, 1, x[0, c], grid[0] * grid[1] * grid[2], *grid)
                 continue
-            raw = _data.read_nifti_raw(p).to(device)
             if norm is None:
                 _data.resample_device(raw, grid, out=x[0, c])
                 continue
@@ -1356,7 +1845,7 @@ def prepare_case_device(case_dir: str, target_size: Optional[Sequence[int]] = (1
                 x[0, c].zero_()
             elif p is None:
                 x[0, c].copy_(x[0, dup])
-    return x
+    return (x, _alignment_report(paths, align, report)) if return_alignment else x
 
 
 @dataclasses.dataclass
@@ -1364,12 +1853,16 @@ class CasePrediction:
     """``ModelPredictor.predict_case``'s result: the uint8 ``mask`` and, when asked for, the fp32
     ``probability`` on the native (z, y, x) grid of ``reference_path``, whose
     ``data.read_nifti_geometry`` is ``geometry``; ``lesions`` is ``lesion_table`` of the mask when
-    ``predict_case`` was asked for it."""
+    ``predict_case`` was asked for it; ``alignment``: with ``align``, per present modality
+    ``{"params": (tz, ty, tx, rz, ry, rx), "before": .., "after": ..}`` -- the rigid correction
+    and the similarity before and after it (zeros and None where nothing was registered) -- else
+    None."""
     mask: np.ndarray
     probability: Optional[np.ndarray]
     reference_path: str
     geometry: dict
     lesions: Optional[List[dict]] = None
+    alignment: Optional[dict] = None
 
 
 def preprocess_image(image: np.ndarray) -> torch.Tensor:
@@ -1411,7 +1904,7 @@ class ModelPredictor:
                      return_probability: bool = False, *, keep_largest: int = 0, min_voxels: int = 0,
                      fill_holes: bool = False, connectivity: int = 26,
                      return_lesions: bool = False, window: Optional[Sequence[int]] = None, overlap=0.5,
-                     blend: str = "gaussian", window_batch: int = 4) -> CasePrediction:
+                     blend: str = "gaussian", window_batch: int = 4, align=None) -> CasePrediction:
         """One case from its raw NIfTI files to a mask on its native grid, on the GPU:
         ``prepare_case_device`` -> the network on the input and on its copies flipped along each
         of ``tta_flips`` (tuples of axes out of 0, 1, 2) in one batch -> pcms_flip_mean
@@ -1435,8 +1928,17 @@ class ModelPredictor:
         ``window_batch * (1 + len(tta_flips))`` windows of one shape; everything after the
         probabilities runs as without a window.  ``window=None``: nothing changes and nothing new
         is launched.  ValueError for a window axis under 16 (the network pools four times) or a
-        bad ``overlap`` / ``blend`` / ``window_batch``."""
+        bad ``overlap`` / ``blend`` / ``window_batch``.
+        ``align`` (keyword-only): ``prepare_case_device``'s -- the modalities are
+        brought onto the reference file's grid through their header geometry (``"world"``) and a
+        rigid registration on the device (``"register"``) instead of being stretched onto it.  The
+        reference defaults to ``output_like``, else the first present modality's file;
+        ``target_size=None`` is its native grid and the modalities' shapes may differ.  The
+        result's ``alignment`` reports the corrections.  ``align=None``: nothing changes."""
         from ._lib import call
+        align = Alignment.of(align)
+        if align is not None and align.to is None and output_like is not None:
+            align = dataclasses.replace(align, to=output_like)
         masks = _flip_masks(tta_flips)
         if window is not None:
             window = _check_sliding(window, overlap, blend, window_batch)
@@ -1445,9 +1947,11 @@ class ModelPredictor:
         _check_filter(keep_largest, min_voxels)
         _offsets(connectivity)
         post = keep_largest != 0 or min_voxels > 1 or bool(fill_holes)
-        x = prepare_case_device(case_dir, target_size, handle_missing, normalise, self.device)  # raises if none present
+        x, alignment = prepare_case_device(case_dir, target_size, handle_missing, normalise, self.device, align,
+                                           return_alignment=True)  # raises if none present
         reference = output_like if output_like is not None else \
-            next(p for p in _case_files(case_dir) if p is not None)
+            next(p for p in _case_files(case_dir) if p is not None) if align is None else \
+            _case_reference(_case_files(case_dir), align)
         native = tuple(int(v) for v in read_nifti_header(reference)["shape_xyz"][:3][::-1])
         geometry = _data.read_nifti_geometry(reference)
         grid = tuple(x.shape[2:])
@@ -1480,7 +1984,7 @@ class ModelPredictor:
                 spacing = tuple(float(v) for v in geometry["pixdim"][1:4])[::-1]
                 lesions = lesion_table_device(mask, prob_native, spacing, connectivity)
         return CasePrediction(mask_host, prob_native.cpu().numpy() if return_probability else None, reference,
-                              geometry, lesions)
+                              geometry, lesions, alignment)
 
     def score_case(self, result: CasePrediction, label_path: str, lesion_metrics: bool = False,
                    min_iou: float = 0.1, connectivity: int = 26) -> dict:

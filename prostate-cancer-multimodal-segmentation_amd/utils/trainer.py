@@ -29,7 +29,10 @@ case and epoch; validation never augments; both loaders give the same batches), 
 (patch training, see ``data.PatchSampling``: every case yields P foreground-biased crops of the
 sliding-window predictor's window shape, a step sees ``batch_size * P`` of them; the validation
 loader cuts patches too, without augmentation and at epoch 0, so the same ones every epoch --
-whole-case sliding-window validation is not part of the trainer), and the step
+whole-case sliding-window validation is not part of the trainer), ``align`` / ``corrections``
+(``predict.Alignment``: every volume of a case is placed on the reference file's grid through its
+NIfTI world geometry, with the rigid corrections of ``predict.register_dataset`` -- a dict or the
+path of its JSON -- when given; training never registers on the fly), and the step
 variants of the other reference trainers:
   ``max_grad_norm``  clip_grad_norm_(max_norm) before Adam (train_bph.py:166,
                      train_bph_cv.py:311 use 1.0): one fused norm pass, the clip coefficient
@@ -124,7 +127,9 @@ class BaseTrainer:
                               augment_seed=int(self.config.get("augment_seed", 0)),
                               # both loaders; the validation dataset's epoch is never moved, so with
                               # augment=None it cuts the same patches every epoch
-                              patches=self.config.get("patches"))
+                              patches=self.config.get("patches"),
+                              # both loaders: the modalities are placed by their header geometry
+                              align=self.config.get("align"), corrections=self.config.get("corrections"))
 
     def _broadcast_params(self):
         eng = self.model.engine()
