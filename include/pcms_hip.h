@@ -418,9 +418,9 @@ int pcms_add(int dtype, void* dst, const void* src, long n, hipStream_t s);
  * (DoubleConv3D / Down3D / Up3D called on their own, models/unet3d.py:42-158)          */
 int pcms_unpack_output(int dtype, const void* in, float* out, int N, int C, int Cs, long V, hipStream_t s);
 
-/* ---- loader: data.resample on the device (script/data_loader.py:240-283, :379-409) --- */
+/* ---- loader: resample.resample on the device (script/data_loader.py:240-283, :379-409) --- */
 /* One source volume -> one D x H x W fp32 plane (a channel of an NCDHW tensor), equal to
- * data.resample of the decoded volume bit for bit.  src: the file's voxels in their native
+ * resample.resample of the decoded volume bit for bit.  src: the file's voxels in their native
  * type, little endian, (Di, Hi, Wi) with W fastest, aligned to the element size; datatype: the
  * NIfTI-1 code (2 u8, 4 i16, 8 i32, 16 f32, 64 f64, 256 i8, 512 u16, 768 u32, 1024 i64, 1280
  * u64).  A voxel's value is (float)((double)raw * slope + inter) when scl_slope is not 0 or 1
@@ -433,11 +433,11 @@ int pcms_resample_linear(const void* src, int datatype, int Di, int Hi, int Wi, 
                          float* out, int D, int H, int W, hipStream_t s);
 /* The label form: index k = floor((double)i * ratio + 0.5) per axis (identity when n_in ==
  * n_out), out = 0 where k >= n_in, else (value > 0 ? 1 : 0) with the value scaled in fp64 as
- * above and, as data.resample returns fp32, rounded to fp32 before the comparison unless the
+ * above and, as resample.resample returns fp32, rounded to fp32 before the comparison unless the
  * volume already has the target shape (ProstateDataset compares that one as read).        */
 int pcms_resample_label(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope, double scl_inter,
                         float* out, int D, int H, int W, hipStream_t s);
-/* Training-time augmentation (data.resample_affine on the device, bit for bit): the same
+/* Training-time augmentation (resample.resample_affine on the device, bit for bit): the same
  * gather under a 3x4 affine.  affine12: twelve HOST doubles, row-major A[3][3] then t[3],
  * copied into the kernel arguments.  Output index (d, h, w) samples source axis a at
  * c_a = ((A[a][0] d + A[a][1] h) + A[a][2] w) + t[a] in fp64, every product and sum rounded on
@@ -455,7 +455,7 @@ int pcms_resample_affine_linear(const void* src, int datatype, int Di, int Hi, i
 int pcms_resample_affine_label(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
                                double scl_inter, const double* affine12, float* out, int D, int H, int W,
                                hipStream_t s);
-/* Elastic deformation in the same launch (data.resample_deform on the device, bit for bit).
+/* Elastic deformation in the same launch (resample.resample_deform on the device, bit for bit).
  * field: gd * gh * gw * 3 DEVICE doubles, the control grid P[gd][gh][gw][3] of a uniform cubic
  * B-spline over the output grid's index space, 8-byte aligned; each workgroup copies it into LDS.
  * For output index i of an axis of extent N with g control points: x = (double)i * ((double)
@@ -481,21 +481,21 @@ int pcms_resample_deform_label(const void* src, int datatype, int Di, int Hi, in
 /* ---- case prediction: predict.py's host forms on the device (script/predict.py) ------ */
 /* lohi[0] / lohi[1]: the minimum / maximum of the n decoded fp32 values of a volume (decoded
  * as pcms_resample_linear decodes a voxel, so a negative scl_slope is seen), what
- * predict.normalise takes from numpy's min / max: a NaN anywhere gives NaN for both.  src
+ * intensity.normalise takes from numpy's min / max: a NaN anywhere gives NaN for both.  src
  * needs its element's alignment only.  Two launches, deterministic: per-workgroup partials in
  * work (pcms_volume_minmax_work_floats(n) floats, device memory), then one workgroup folds them.
  * An unknown datatype, n < 1, a NULL or misaligned pointer: negative, no launch.            */
 int pcms_volume_minmax_work_floats(long n);
 int pcms_volume_minmax(const void* src, int datatype, long n, double scl_slope, double scl_inter, float* lohi,
                        float* work, hipStream_t s);
-/* pcms_resample_linear with every source voxel v replaced by predict.normalise's value: with
+/* pcms_resample_linear with every source voxel v replaced by intensity.normalise's value: with
  * lo = lohi[0], hi = lohi[1] (DEVICE floats, e.g. pcms_volume_minmax's) and den =
  * fl32((double)hi - (double)lo), the corner is fl32(fl32(v - lo) / den), or 0 when den == 0.
- * Equal to data.resample(predict.normalise(vol), (D, H, W)) bit for bit; with all three axes
+ * Equal to resample.resample(intensity.normalise(vol), (D, H, W)) bit for bit; with all three axes
  * identical a plain normalise.  Rejects what pcms_resample_linear rejects and a NULL lohi.    */
 int pcms_resample_linear_norm(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
                               double scl_inter, const float* lohi, float* out, int D, int H, int W, hipStream_t s);
-/* predict.tta_mean: probs holds k contiguous D x H x W fp32 volumes, volume j computed from the
+/* window.tta_mean: probs holds k contiguous D x H x W fp32 volumes, volume j computed from the
  * input flipped along the axes in flipmask[j] (bit 0: D, bit 1: H, bit 2: W; k HOST ints copied
  * into the kernel arguments).  out = (((p0 + flip(p1)) + flip(p2)) + ...) / (float)k, every fp32
  * sum and the quotient rounded on its own; out must not overlap probs.  1 <= k <= 8 (the
@@ -509,7 +509,7 @@ int pcms_flip_mean(const float* probs, int k, const int* flipmask, float* out, i
 int pcms_prob_to_mask(const float* prob, int Dt, int Ht, int Wt, float threshold, unsigned char* mask,
                       float* prob_native, int D, int H, int W, hipStream_t s);
 
-/* ---- mask post-processing: predict.py's label_components / postprocess on the device ---- */
+/* ---- mask post-processing: components.py's label_components / postprocess on the device ---- */
 /* Foreground is mask != 0 (mask == 0 with invert = 1), the flat index of a voxel is
  * (d H + h) W + w, connectivity is 6, 18 or 26 (offsets in {-1, 0, 1}, at most 1 / 2 / 3 of
  * them nonzero).  work: pcms_components_work_ints(D, H, W) int32 of device memory (negative for
@@ -522,17 +522,17 @@ int pcms_prob_to_mask(const float* prob, int Dt, int Ht, int Wt, float threshold
  * overlapping mask: negative, no launch, outputs and work untouched.                        */
 int pcms_components_work_ints(int D, int H, int W);
 /* labels[i] = 0 on background, 1 + the smallest flat index of the voxel's component on
- * foreground (predict.label_components): a function of the mask alone, deterministic.       */
+ * foreground (components.label_components): a function of the mask alone, deterministic.       */
 int pcms_components_label(const unsigned char* mask, int invert, int connectivity, int* labels, int* work, int D,
                           int H, int W, hipStream_t s);
-/* predict.postprocess byte for byte: components ranked by (size descending, label ascending);
+/* components.postprocess byte for byte: components ranked by (size descending, label ascending);
  * one stays iff size >= min_voxels and (keep_largest == 0 or rank < keep_largest); then, with
  * fill_holes != 0, every 6-connected background component that touches none of the six faces
  * of the volume becomes 1.  out holds 0 / 1 bytes.                                           */
 int pcms_mask_postprocess(const unsigned char* mask, unsigned char* out, int* work, int keep_largest, int min_voxels,
                           int fill_holes, int connectivity, int D, int H, int W, hipStream_t s);
 
-/* ---- surface distances: predict.py's surface / edt_sq / surface_metrics on the device ------ */
+/* ---- surface distances: distance.py's surface / edt_sq / surface_metrics on the device ----- */
 /* Volumes are (D, H, W) with W fastest; foreground / feature is byte != 0.  Every axis is at
  * most 2048 long (the H and D passes stage whole lines in LDS) and the volume at most
  * 2^30 - 4096 voxels; pcms_edt_work_bytes(D, H, W) is the bytes of device workspace all three
@@ -542,16 +542,16 @@ int pcms_mask_postprocess(const unsigned char* mask, unsigned char* out, int* wo
  * workspace overlapping an input or one another: negative, no launch, outputs and work untouched. */
 int pcms_edt_work_bytes(int D, int H, int W);
 /* out[i] = 1 where voxel i is foreground and one of its six face neighbours is background or
- * lies outside the volume, else 0 (predict.surface).                                          */
+ * lies outside the volume, else 0 (distance.surface).                                          */
 int pcms_mask_surface(const unsigned char* mask, unsigned char* out, int D, int H, int W, hipStream_t s);
-/* predict.edt_sq bit for bit: out[p] (fp64) = min over feature voxels q of
+/* distance.edt_sq bit for bit: out[p] (fp64) = min over feature voxels q of
  * fl(Z(|pd-qd|) + fl(Y(|ph-qh|) + X(|pw-qw|))), X(k) = fl(fl(k sx) fl(k sx)) and Y, Z alike with
  * spacing = {sz, sy, sx}: three HOST doubles copied into the kernel arguments; +inf everywhere
  * when feat has no feature voxel.  Three launches (W, H, D passes), no atomics, every loop
  * bounded by an axis length.                                                                   */
 int pcms_edt_sq(const unsigned char* feat, const double* spacing, double* out, void* work, int D, int H, int W,
                 hipStream_t s);
-/* One direction of predict.surface_metrics.  sq_b: pcms_edt_sq of b's surface.  sd_sq_out[i] =
+/* One direction of distance.surface_metrics.  sq_b: pcms_edt_sq of b's surface.  sd_sq_out[i] =
  * sq_b[i] at the voxels of surface(mask_a) (computed here), -1.0 elsewhere.  stats (device, 24
  * bytes, 8-byte aligned): [0] the number of surface voxels as int64, [1] the maximum of
  * sd_sq_out as a double (-1.0 without a surface voxel), [2] the sum of sqrt(sd_sq_out) over the
@@ -560,7 +560,7 @@ int pcms_edt_sq(const unsigned char* feat, const double* spacing, double* out, v
 int pcms_surface_distance_stats(const unsigned char* mask_a, const double* sq_b, double* sd_sq_out, void* stats,
                                 void* work, int D, int H, int W, hipStream_t s);
 
-/* ---- lesion analysis: predict.py's component_table on the device ------------------------- */
+/* ---- lesion analysis: lesions.py's component_table on the device ------------------------- */
 /* labels: a canonical label volume (pcms_components_label's output: 0 on background, 1 + the
  * smallest flat index of the component elsewhere).  Voxel i is a root iff labels[i] == i + 1; the
  * row of a component is the number of roots below its own, so rows are in ascending label order.
@@ -592,7 +592,7 @@ int pcms_component_table_bytes(int capacity, int with_prob);
 int pcms_component_table(const int* labels, const float* prob, void* table, int capacity, int* header, void* work,
                          int D, int H, int W, hipStream_t s);
 
-/* ---- sliding-window prediction: predict.py's gather_windows / blend_windows on the device ---- */
+/* ---- sliding-window prediction: window.py's gather_windows / blend_windows on the device ----- */
 /* A window is a wd x wh x ww box of a D x H x W volume (W fastest) at a start (sd, sh, sw): three
  * int32 of a DEVICE table; it may stick out past the volume.  flipmask: k HOST ints copied into
  * the kernel arguments, bit 0 / 1 / 2 = the window is mirrored along its D / H / W axis, 1 <= k
@@ -601,7 +601,7 @@ int pcms_component_table(const int* labels, const float* prob, void* table, int 
  * synchronisation, no atomics.  A NULL or misaligned pointer, a size < 1, k outside 1..8,
  * flipmask[0] != 0 or an entry outside 0..7, a window axis above 512, first_window < 0:
  * negative, no launch.                                                                        */
-/* predict.gather_windows for the B windows of starts[B][3]: out is (B k, C, wd, wh, ww) fp32, all
+/* window.gather_windows for the B windows of starts[B][3]: out is (B k, C, wd, wh, ww) fp32, all
  * of it written; entry i k + j at (c, a, b, e) is x[c] at start_i + (a', b', e'), the primed index
  * mirrored (n - 1 - index) along the axes of flipmask[j], or 0.f where that lies outside the
  * volume (a start is not checked: whatever it is, nothing outside x is read).  One thread forms
@@ -609,7 +609,7 @@ int pcms_component_table(const int* labels, const float* prob, void* table, int 
  * x is (C, D, H, W) fp32 and must not overlap out.  B k C must fit an int.                     */
 int pcms_window_gather(const float* x, int C, int D, int H, int W, const int* starts, int B, const int* flipmask, int k,
                        int wd, int wh, int ww, float* out, hipStream_t s);
-/* predict.blend_windows for windows first_window .. first_window + B - 1 of the whole table
+/* window.blend_windows for windows first_window .. first_window + B - 1 of the whole table
  * starts (row = window index); probs is (B k, wd, wh, ww) fp32, the batch's probabilities in
  * pcms_window_gather's entry order.  wts: wd + wh + ww DEVICE floats, the three per-axis tables
  * one after the other.  One thread per voxel of the batch's bounding box (found on the device,
@@ -669,8 +669,8 @@ int pcms_patch_resample_linear(const void* src, int datatype, int Di, int Hi, in
                                int Gd, int Gh, int Gw, const int* origins, int P, float* out, long patch_stride, int D,
                                int H, int W, hipStream_t s);
 
-/* ---- percentile intensity window: predict.py's intensity_window / normalise_window --------- */
-/* predict.intensity_window on the device, bit for bit: lohi[0] / lohi[1] (DEVICE floats) are the
+/* ---- percentile intensity window: intensity.py's intensity_window / normalise_window ------- */
+/* intensity.intensity_window on the device, bit for bit: lohi[0] / lohi[1] (DEVICE floats) are the
  * values at ranks r_lo / r_hi of the ascending order of the selected voxels.  A voxel is decoded as
  * pcms_volume_minmax decodes it and replaced by v + 0.f (-0 becomes +0); the selected set is every
  * voxel, or with use_above != 0 the voxels with v > above (never a NaN); m is its size.  ppm_lo <
@@ -694,15 +694,15 @@ int pcms_patch_resample_linear(const void* src, int datatype, int Di, int Hi, in
 int pcms_volume_window_work_bytes(long n);
 int pcms_volume_window(const void* src, int datatype, long n, double scl_slope, double scl_inter, int ppm_lo,
                        int ppm_hi, int use_above, float above, float* lohi, void* work, hipStream_t s);
-/* pcms_resample_linear_norm with predict.normalise_window's corner: with lo = lohi[0], hi =
+/* pcms_resample_linear_norm with intensity.normalise_window's corner: with lo = lohi[0], hi =
  * lohi[1] (DEVICE floats, e.g. pcms_volume_window's) and den = fl32((double)hi - (double)lo), a
  * source voxel v becomes c = v < lo ? lo : v > hi ? hi : v (a NaN stays), then fl32(fl32(c - lo)
- * / den), or 0 when den == 0.  Equal to data.resample(predict.normalise_window(vol, lohi), (D, H,
+ * / den), or 0 when den == 0.  Equal to resample.resample(intensity.normalise_window(vol, lohi), (D, H,
  * W)) bit for bit.  Rejects what pcms_resample_linear_norm rejects.                            */
 int pcms_resample_linear_window(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
                                 double scl_inter, const float* lohi, float* out, int D, int H, int W, hipStream_t s);
 /* pcms_patch_resample_linear with that corner: data.resample_patch of
- * predict.normalise_window(vol, lohi), bit for bit.  lohi is required; every other argument, the
+ * intensity.normalise_window(vol, lohi), bit for bit.  lohi is required; every other argument, the
  * 16-byte / scalar store rule and the rejections are pcms_patch_resample_linear's, and a NULL
  * lohi is rejected too.                                                                        */
 int pcms_patch_resample_window(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
@@ -710,8 +710,8 @@ int pcms_patch_resample_window(const void* src, int datatype, int Di, int Hi, in
                                int Gd, int Gh, int Gw, const int* origins, int P, float* out, long patch_stride, int D,
                                int H, int W, hipStream_t s);
 
-/* ---- modality alignment: predict.py's joint_histogram ------------------------------------- */
-/* predict.joint_histogram on the device, on the counts exactly: the joint intensity histogram of
+/* ---- modality alignment: align.py's joint_histogram --------------------------------------- */
+/* align.joint_histogram on the device, on the counts exactly: the joint intensity histogram of
  * a fixed and a moving raw volume under an affine, the table a mutual-information similarity is
  * formed from.  The lattice is every (sd, sh, sw)-th voxel of the fixed volume, q = (a sd, b sh,
  * e sw) with q inside (Df, Hf, Wf).  For a lattice voxel q: the moving coordinate is c_a =

@@ -1,4 +1,4 @@
-// The similarity of rigid registration on the device (gfx950): predict.py's host form
+// The similarity of rigid registration on the device (gfx950): align.py's host form
 // joint_histogram evaluated on two raw NIfTI volumes, on the counts exactly.
 //
 //   pcms_joint_histogram  hist[bf][bm] = the number of lattice voxels q of the fixed volume whose
@@ -67,7 +67,7 @@ __device__ __forceinline__ float fixed_value(const void* p, int code, long x, co
   }
 }
 
-// predict._bin_index: fl32(v * (float)bins) clamped to [0, bins - 1] as a float, then truncated
+// align._bin_index: fl32(v * (float)bins) clamped to [0, bins - 1] as a float, then truncated
 // (for v in [0, 1] that is min((int)fl32(v bins), bins - 1)); v is not a NaN
 __device__ __forceinline__ uint32_t bin_of(float v, float fbins, float top) {
   const float b = v * fbins;

@@ -1,4 +1,4 @@
-// Mask post-processing on the device (gfx950): predict.py's host forms label_components /
+// Mask post-processing on the device (gfx950): components.py's host forms label_components /
 // filter_components / fill_holes / postprocess, byte for byte.
 //
 //   pcms_components_label   canonical labels: 0 on background, 1 + the smallest flat index of

@@ -1,4 +1,4 @@
-// Elastic deformation in the augmenting resample launch (gfx950): data.resample_deform per output
+// Elastic deformation in the augmenting resample launch (gfx950): resample.resample_deform per output
 // voxel, bit for bit.  A smooth displacement u(d, h, w) -- a uniform cubic B-spline of one fp64
 // control grid P[gd][gh][gw][3] per case, evaluated in the output grid's index space -- is added
 // to the output index before the affine of resample.hip's augmenting kernels: p'_a = (double)

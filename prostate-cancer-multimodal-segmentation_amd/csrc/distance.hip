@@ -1,4 +1,4 @@
-// Surface distances on the device (gfx950): predict.py's host forms surface / edt_sq and the
+// Surface distances on the device (gfx950): distance.py's host forms surface / edt_sq and the
 // per-direction statistics of surface_metrics, the transform bit for bit.
 //
 //   pcms_mask_surface            surface(mask): foreground with a face neighbour that is

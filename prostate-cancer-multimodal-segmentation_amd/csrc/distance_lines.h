@@ -3,7 +3,7 @@
 // templated on a memory policy `Mem` that supplies the line it reads,
 //   T load(int i) const      element i of the line, 0 <= i < the line's length
 //
-// The value defined (predict.edt_sq) is, per voxel p and spacing (sz, sy, sx),
+// The value defined (distance.edt_sq) is, per voxel p and spacing (sz, sy, sx),
 //   min over feature voxels q of  fl( Z(|pd-qd|) + fl( Y(|ph-qh|) + X(|pw-qw|) ) )
 //   X(k) = fl(fl(k sx) fl(k sx)), Y and Z alike                          (sq_term)
 // and +inf without a feature voxel.  fp64 addition is monotone in each argument and X, Y, Z are

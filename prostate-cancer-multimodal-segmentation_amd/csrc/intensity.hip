@@ -1,4 +1,4 @@
-// Percentile intensity normalisation on the device (gfx950): predict.py's host forms
+// Percentile intensity normalisation on the device (gfx950): intensity.py's host forms
 // intensity_window / normalise_window evaluated on a raw NIfTI volume, bit for bit.
 //
 //   pcms_volume_window           lohi = the values at two ranks of the selected voxels' sorted

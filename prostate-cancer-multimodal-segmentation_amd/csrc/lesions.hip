@@ -1,4 +1,4 @@
-// The component table on the device (gfx950): predict.py's component_table, on the bytes.
+// The component table on the device (gfx950): lesions.py's component_table, on the bytes.
 //
 //   pcms_component_table   one row per component of a canonical label volume (0 on background,
 //                          1 + the smallest flat index of the component elsewhere), in ascending

@@ -192,7 +192,7 @@ __global__ void __launch_bounds__(TPB) foreground_pick_kernel(const float* __res
 // (an origin is device memory and is not trusted) and exact as a double; the voxel is 0 where q
 // leaves the grid, else resample_affine's value at q: the coordinate, the inside rule on the
 // doubles -- so nothing outside src is read wherever q lies -- the lerps and the intensity step.
-// NORM: every corner is predict.normalise's value, as in pcms_resample_linear_norm.  vec (W % 4
+// NORM: every corner is intensity.normalise's value, as in pcms_resample_linear_norm.  vec (W % 4
 // == 0, out and stride 16-byte aligned): one 16-byte store, else up to four scalars.
 // Registers: the four elements are a rolled loop whose row indices pass through an empty asm, so
 // that the row's three partial coordinate sums are formed per element instead of staying live

@@ -1,12 +1,12 @@
 // Device-side resampling of one NIfTI volume to the training grid (gfx950): the loader's
-// data.resample (the reference's ResampleImageFilter geometry, script/data_loader.py:258-281
+// resample.resample (the reference's ResampleImageFilter geometry, script/data_loader.py:258-281
 // linear for images, :383-406 nearest for labels) evaluated per output voxel, bit for bit.
 //
 // The source is the file's voxel bytes in their native type (NIfTI datatype code, little
 // endian, (Di, Hi, Wi) with W fastest); the header's scl_slope / scl_inter are applied on the
 // fly by read_nifti's rule.  Output index i of an axis samples the continuous input index
 // c = (double)i * (n_in / n_out), the fp64 expression numpy forms (exact rational indices
-// disagree with it for many size pairs).  data.resample runs three separable fp64 passes
+// disagree with it for many size pairs).  resample.resample runs three separable fp64 passes
 // (D, then H, then W); an 8-corner gather lerped in that order gives every intermediate the
 // same two operands and so the same roundings.  Every product and sum below must round on its
 // own, as numpy's do: no contraction into FMAs anywhere in this file.
@@ -44,7 +44,7 @@ __device__ __forceinline__ long nearest_index(const Axis& a, int i) {
   return k < a.n_in ? k : -1;
 }
 
-// round32: data.resample's result is fp32 before the loader's `> 0`; a volume already of the
+// round32: resample.resample's result is fp32 before the loader's `> 0`; a volume already of the
 // target shape is not resampled and is compared as read (ProstateDataset.__getitem__)
 template <typename T>
 __global__ void __launch_bounds__(TPB) resample_label_kernel(const T* __restrict__ src, float* __restrict__ out,
@@ -98,7 +98,7 @@ int resample(bool label, const void* src, int code, int Di, int Hi, int Wi, doub
   return for_datatype(code, [&](auto t) { return launch<decltype(t)>(label, src, out, ad, ah, aw, sc, s); });
 }
 
-// ---- training-time augmentation: the same gather under a full 3x4 affine (data.resample_affine) ----
+// ---- training-time augmentation: the same gather under a full 3x4 affine (resample.resample_affine) ----
 // The coordinate, the inside rules and the gather are resample_common.h's (deform.hip shares them).
 template <typename T>
 __global__ void __launch_bounds__(TPB) resample_affine_linear_kernel(const T* __restrict__ src, float* __restrict__ out,

@@ -1,7 +1,7 @@
 // What the resampling kernels of resample.hip (loader, augmentation), deform.hip (elastic
 // augmentation), predict.hip (case prediction), patch.hip (patch training), intensity.hip
 // (percentile intensity window) and align.hip (joint histogram) share: the per-axis geometry and
-// the 8-corner gather of data.resample, the coordinate, inside rules and gather of data.resample_affine,
+// the 8-corner gather of resample.resample, the coordinate, inside rules and gather of resample.resample_affine,
 // read_nifti's decoding of a voxel and the dispatch over the NIfTI datatype codes.  Every product and sum must
 // round on its own, as numpy's do: no contraction into FMAs from here to the end of the
 // including file.
@@ -67,7 +67,7 @@ __device__ __forceinline__ Tap linear_tap(const Axis& a, int i) {
 }
 __device__ __forceinline__ double lerp(double a, double b, double w) { return a * (1.0 - w) + b * w; }
 
-// The 8-corner gather of data.resample at one output voxel whose taps are all inside:
+// The 8-corner gather of resample.resample at one output voxel whose taps are all inside:
 // corner(index) is a source voxel as the fp64 value the host's first pass reads; the lerps run
 // over D, then H, then W, an identity axis copied, one rounding to fp32
 template <typename Corner>
@@ -90,7 +90,7 @@ __device__ __forceinline__ float gather_linear(const Axis& ad, const Axis& ah, c
   return (float)(aw.ident ? vh[0] : lerp(vh[0], vh[1], tw.w));
 }
 
-// ---- the gather under a full 3x4 affine (data.resample_affine; resample.hip and deform.hip) ----
+// ---- the gather under a full 3x4 affine (resample.resample_affine; resample.hip and deform.hip) ----
 // Output position (d, h, w) samples the source at c_a = ((A[a][0] d + A[a][1] h) + A[a][2] w) + t[a]
 // (fp64, every product and sum rounded on its own, in this order); with A = diag(n_in / n_out)
 // and t = 0 that is the plain kernels' coordinate.  A coordinate may lie anywhere (or be
@@ -114,7 +114,7 @@ inline Affine make_affine(const double* a) {
 __device__ __forceinline__ double affine_coord(const Row& r, double d, double h, double w) {
   return ((r.x * d + r.y * h) + r.z * w) + r.t;
 }
-// ITK's buffer rule (data._axis_linear): inside iff -0.5 <= c < n - 0.5; false for NaN
+// ITK's buffer rule (resample._axis_linear): inside iff -0.5 <= c < n - 0.5; false for NaN
 __device__ __forceinline__ bool linear_inside(double c, int n) { return c >= -0.5 && c < (double)n - 0.5; }
 // neighbours floor(c), floor(c) + 1 of an inside coordinate, each clamped to [0, n - 1] (c may be
 // below 0 here: the lower clamp binds)
@@ -169,13 +169,13 @@ __device__ __forceinline__ float affine_linear_value(const T* __restrict__ src, 
                               [&](long x) { return (double)image_value(src[x], sc); });
 }
 
-// predict.normalise of one decoded value: den = fl32((double)hi - (double)lo), formed per thread
+// intensity.normalise of one decoded value: den = fl32((double)hi - (double)lo), formed per thread
 __device__ __forceinline__ float normalised(float v, float lo, float den) {
   return den == 0.f ? 0.f : (v - lo) / den;
 }
 
-// predict.normalise_window of one decoded value: the clip written with comparisons (a NaN passes
-// through), then predict.normalise's difference and quotient
+// intensity.normalise_window of one decoded value: the clip written with comparisons (a NaN passes
+// through), then intensity.normalise's difference and quotient
 __device__ __forceinline__ float windowed(float v, float lo, float hi, float den) {
   if (den == 0.f) return 0.f;
   const float c = v < lo ? lo : v > hi ? hi : v;
@@ -216,7 +216,7 @@ inline bool affine_args_ok(const void* src, const float* out, const double* a, i
   return std::isfinite(gain) && std::isfinite(bias);
 }
 
-// f(T{}) for the element type of a NIfTI-1 datatype code (data._NIFTI_DTYPES); -1: no such code
+// f(T{}) for the element type of a NIfTI-1 datatype code (nifti._NIFTI_DTYPES); -1: no such code
 template <typename F> int for_datatype(int code, F&& f) {
   switch (code) {
     case 2: return f(uint8_t{});

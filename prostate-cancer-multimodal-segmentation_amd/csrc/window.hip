@@ -1,4 +1,4 @@
-// Sliding-window prediction on the device (gfx950): predict.py's host forms gather_windows /
+// Sliding-window prediction on the device (gfx950): window.py's host forms gather_windows /
 // blend_windows evaluated per voxel, bit for bit.
 //
 //   pcms_window_gather   a batch of B windows (and their flipped copies) cut out of a (C, D, H, W)

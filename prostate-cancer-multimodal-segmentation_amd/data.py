@@ -1,13 +1,9 @@
 """Input pipeline feeding ``Trainer.step`` (reference script/data_loader.py).
 
-The reference reads NIfTI volumes with SimpleITK, which is absent here, so this module has
-its own NIfTI-1 reader (``read_nifti``: .nii / .nii.gz, the header's scl_slope/scl_inter
-applied, array in SimpleITK ``GetArrayFromImage`` order (z, y, x)) and its own resampler
-(``resample``: the reference's ResampleImageFilter set-up — same origin and direction,
-output spacing = size * spacing / target, linear for images, nearest for labels).  The
-resampler is ITK's index mapping restated (output index i samples input continuous index
-i * n_in / n_out); without SimpleITK its results are parity-unpinned beyond the tests'
-closed-form cases (identity, integer down-sampling, constant and linear ramps).
+The reference reads and resamples NIfTI volumes with SimpleITK, which is absent here: the reader
+is ``nifti`` (``read_nifti`` / ``read_nifti_raw``), the resampler ``resample`` (``resample`` /
+``resample_affine`` / ``resample_deform`` / ``resample_device``), the affines come from
+``geometry``; every public name of those modules is also a name of this one.
 
 Dataset semantics follow script/data_loader.py:
   * case discovery from ``<data_dir>/BPH-PCA/<data_type>/ADC/*.nii[.gz]`` (:57-94);
@@ -38,11 +34,11 @@ grid, a chosen share centred on a lesion voxel -- ``draw_patches`` / ``pick_orig
 ``resample_patch`` on the host, pcms_foreground_pick / pcms_patch_resample_linear in
 ``assemble_patch_batch``, the origins chosen and consumed on the device; the same batches bit
 for bit once more.
-``align=...`` (a ``predict.Alignment``; dataset, loader, ``Trainer`` config) places every volume of
+``align=...`` (an ``align.Alignment``; dataset, loader, ``Trainer`` config) places every volume of
 a case on the reference file's grid through the files' world geometry instead of stretching it
 onto the grid: ``world_matrix`` / ``align_affine`` / ``compose_affine`` / ``case_affine`` on the
 host, the same twelve doubles per volume in the existing affine launches on the device, with the
-rigid ``corrections`` of ``predict.register_dataset`` when given; the same batches bit for bit.
+rigid ``corrections`` of ``align.register_dataset`` when given; the same batches bit for bit.
 The reference's SimpleITK ``SetSize`` takes (x, y, z), so its non-cubic outputs come out
 axis-reversed; here ``target_size`` is (D, H, W) as documented (:41).
 """
@@ -51,350 +47,28 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 import glob
-import gzip
 import os
-import struct
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
+from ._args import axes3, host_affine12, host_ints
+from ._lib import call, query
+from .align import Alignment
+from .geometry import (RIGID_NAMES, affine12_of, align_affine, case_affine, compose_affine,  # noqa: F401
+                       compose_transform, registration_fixed, rigid_correction, rigid_world, volume_affine,
+                       world_centre, world_matrix)
+from .intensity import Normalisation, _lohi_enqueue
+from .nifti import (_NIFTI_DTYPES, RawVolume, _shape_zyx, device_raw, read_nifti,  # noqa: F401
+                    read_nifti_geometry, read_nifti_header, read_nifti_raw, write_nifti)
+from .resample import (MAX_CONTROL_POINTS, _sample_at, field_displacement, resample,  # noqa: F401
+                       resample_affine, resample_deform, resample_device)
+from .window import gather_windows
+
+
 DEFAULT_MODALITIES = ["ADC", "DWI", "gaoqing-T2", "T2 fs", "T2 not fs"]
-
-# NIfTI-1 datatype codes -> numpy dtypes
-_NIFTI_DTYPES = {2: np.uint8, 4: np.int16, 8: np.int32, 16: np.float32, 64: np.float64, 256: np.int8,
-                 512: np.uint16, 768: np.uint32, 1024: np.int64, 1280: np.uint64}
-
-
-def _open(path: str):
-    return gzip.open(path, "rb") if path.endswith(".gz") else open(path, "rb")
-
-
-def read_nifti_header(path: str) -> dict:
-    """Parse the 348-byte NIfTI-1 header (either byte order); ValueError if it is not one."""
-    with _open(path) as f:
-        raw = f.read(348)
-    if len(raw) < 348:
-        raise ValueError(f"{path}: truncated NIfTI header")
-    for endian in ("<", ">"):
-        if struct.unpack(endian + "i", raw[:4])[0] == 348:
-            break
-    else:
-        raise ValueError(f"{path}: not a NIfTI-1 file (sizeof_hdr != 348)")
-    dim = struct.unpack(endian + "8h", raw[40:56])
-    datatype, bitpix = struct.unpack(endian + "hh", raw[70:74])
-    pixdim = struct.unpack(endian + "8f", raw[76:108])
-    vox_offset, scl_slope, scl_inter = struct.unpack(endian + "fff", raw[108:120])
-    magic = raw[344:348]
-    if magic not in (b"n+1\x00", b"ni1\x00"):
-        raise ValueError(f"{path}: bad NIfTI magic {magic!r}")
-    if datatype not in _NIFTI_DTYPES:
-        raise ValueError(f"{path}: unsupported NIfTI datatype {datatype}")
-    nd = dim[0]
-    if not 1 <= nd <= 7:
-        raise ValueError(f"{path}: bad dim[0] = {nd}")
-    return {"endian": endian, "shape_xyz": tuple(int(d) for d in dim[1:1 + nd]), "datatype": datatype,
-            "bitpix": bitpix, "spacing": tuple(float(p) for p in pixdim[1:1 + nd]),
-            "vox_offset": int(vox_offset), "scl_slope": float(scl_slope), "scl_inter": float(scl_inter)}
-
-
-def read_nifti(path: str) -> np.ndarray:
-    """Voxel array in SimpleITK ``GetArrayFromImage`` order: (z, y, x), or (t, z, y, x).
-    Intensity scaling (scl_slope != 0) is applied, as ITK's NIfTI reader does."""
-    h = read_nifti_header(path)
-    dt = np.dtype(_NIFTI_DTYPES[h["datatype"]]).newbyteorder(h["endian"])
-    count = int(np.prod(h["shape_xyz"]))
-    with _open(path) as f:
-        f.read(max(h["vox_offset"], 352))
-        buf = f.read(count * dt.itemsize)
-    if len(buf) < count * dt.itemsize:
-        raise ValueError(f"{path}: truncated voxel data")
-    arr = np.frombuffer(buf, dtype=dt, count=count).reshape(h["shape_xyz"][::-1])
-    if h["scl_slope"] not in (0.0, 1.0) or h["scl_inter"] != 0.0:
-        slope = h["scl_slope"] if h["scl_slope"] != 0.0 else 1.0
-        arr = arr.astype(np.float64) * slope + h["scl_inter"]
-    return np.ascontiguousarray(arr)
-
-
-@dataclasses.dataclass
-class RawVolume:
-    """The first 3-D volume of a NIfTI file as stored: its voxel bytes (1-D ``torch.uint8``,
-    little endian), the NIfTI datatype code, the (D, H, W) shape and the header's scaling --
-    what ``resample_device`` needs to form ``read_nifti``'s values on the GPU."""
-    data: torch.Tensor
-    code: int
-    shape: Tuple[int, int, int]
-    slope: float
-    inter: float
-
-    def pin_memory(self) -> "RawVolume":  # DataLoader(pin_memory=True) calls this on custom types
-        return dataclasses.replace(self, data=self.data.pin_memory())
-
-    def to(self, device, non_blocking: bool = False) -> "RawVolume":
-        return dataclasses.replace(self, data=self.data.to(device, non_blocking=non_blocking))
-
-    def numpy(self) -> np.ndarray:
-        """The volume as ``read_nifti`` returns it (host bytes only)."""
-        dt = np.dtype(_NIFTI_DTYPES[self.code]).newbyteorder("<")
-        arr = np.frombuffer(self.data.numpy().tobytes(), dtype=dt).reshape(self.shape)
-        if self.slope not in (0.0, 1.0) or self.inter != 0.0:
-            arr = arr.astype(np.float64) * (self.slope if self.slope != 0.0 else 1.0) + self.inter
-        return np.ascontiguousarray(arr)
-
-
-def read_nifti_raw(path: str) -> RawVolume:
-    """The first 3-D volume of ``path`` undecoded (a 4-D file contributes volume 0, as
-    ``ProstateDataset._first_volume`` takes it); a big-endian file is byte-swapped here."""
-    h = read_nifti_header(path)
-    if len(h["shape_xyz"]) not in (3, 4):
-        raise ValueError(f"unsupported image dimensions: {h['shape_xyz'][::-1]}")
-    dt = np.dtype(_NIFTI_DTYPES[h["datatype"]]).newbyteorder(h["endian"])
-    shape = tuple(int(v) for v in h["shape_xyz"][:3][::-1])
-    nbytes = int(np.prod(shape)) * dt.itemsize
-    with _open(path) as f:
-        f.read(max(h["vox_offset"], 352))
-        buf = f.read(nbytes)
-    if len(buf) < nbytes:
-        raise ValueError(f"{path}: truncated voxel data")
-    arr = np.frombuffer(buf, dtype=dt)
-    if h["endian"] == ">":
-        arr = arr.astype(dt.newbyteorder("<"))
-    data = torch.from_numpy(arr.view(np.uint8).copy())
-    return RawVolume(data, int(h["datatype"]), shape, h["scl_slope"], h["scl_inter"])
-
-
-# the header fields that place a volume in space: (name, byte offset, struct format)
-_GEOMETRY_FIELDS = (("pixdim", 76, "4f"), ("xyzt_units", 123, "B"), ("qform_code", 252, "h"), ("sform_code", 254, "h"),
-                    ("quatern_b", 256, "f"), ("quatern_c", 260, "f"), ("quatern_d", 264, "f"),
-                    ("qoffset_x", 268, "f"), ("qoffset_y", 272, "f"), ("qoffset_z", 276, "f"),
-                    ("srow_x", 280, "4f"), ("srow_y", 296, "4f"), ("srow_z", 312, "4f"))
-
-
-def read_nifti_geometry(path: str) -> dict:
-    """Where the file's voxel grid lies in space (either byte order): ``pixdim`` (pixdim[0..3],
-    qfac first), ``xyzt_units``, ``qform_code`` / ``sform_code``, ``quatern_b/c/d``,
-    ``qoffset_x/y/z`` and ``srow_x/y/z`` (four floats each) -- what SimpleITK's
-    ``CopyInformation`` carries over as spacing, origin and direction, and what
-    ``write_nifti(..., geometry=...)`` writes back."""
-    endian = read_nifti_header(path)["endian"]
-    with _open(path) as f:
-        raw = f.read(348)
-    geo = {}
-    for name, off, fmt in _GEOMETRY_FIELDS:
-        v = struct.unpack_from(endian + fmt, raw, off)
-        geo[name] = v[0] if len(v) == 1 else tuple(v)
-    return geo
-
-
-def write_nifti(path: str, arr_zyx: np.ndarray, spacing: Sequence[float] = (1.0, 1.0, 1.0),
-                geometry: Optional[dict] = None) -> None:
-    """Minimal NIfTI-1 writer (single file, little endian) for tests, synthetic data and
-    predicted masks.  ``geometry`` (a ``read_nifti_geometry`` dict): its fields are written too
-    and ``spacing`` is taken from its pixdim[1..3]; without it the header carries the spacing
-    alone."""
-    codes = {np.dtype(v): k for k, v in _NIFTI_DTYPES.items()}
-    a = np.ascontiguousarray(arr_zyx)
-    if a.dtype not in codes:
-        a = a.astype(np.float32)
-    a = a.astype(a.dtype.newbyteorder("<"))
-    shape_xyz = a.shape[::-1]
-    hdr = bytearray(352)
-    struct.pack_into("<i", hdr, 0, 348)
-    dims = [len(shape_xyz)] + list(shape_xyz) + [1] * (7 - len(shape_xyz))
-    struct.pack_into("<8h", hdr, 40, *dims)
-    struct.pack_into("<hh", hdr, 70, codes[a.dtype], a.dtype.itemsize * 8)
-    pix =[1.0] + list(spacing) + [1.0] * (7 - len(spacing))
-    struct.pack_into("<8f", hdr, 76, *pix[:8])
-    struct.pack_into("<fff", hdr, 108, 352.0, 1.0, 0.0)
-    if geometry is not None:  # pixdim[0..3] among them: the geometry's spacing replaces `spacing`
-        for name, off, fmt in _GEOMETRY_FIELDS:
-            v = geometry[name]
-            struct.pack_into("<" + fmt, hdr, off, *(v if isinstance(v, (tuple, list)) else (v,)))
-    hdr[344:348] = b"n+1\x00"
-    data = bytes(hdr) + a.tobytes()
-    with (gzip.open(path, "wb") if path.endswith(".gz") else open(path, "wb")) as f:
-        f.write(data)
-
-
-def _axis_linear(a: np.ndarray, axis: int, n_out: int) -> np.ndarray:
-    """ITK linear resampling along one axis: output i samples continuous input index
-    c = i * n_in / n_out; neighbours clamped at the border, zero outside [-0.5, n_in - 0.5)."""
-    n_in = a.shape[axis]
-    if n_in == n_out:
-        return a
-    c = np.arange(n_out, dtype=np.float64) * (n_in / n_out)
-    inside = (c >= -0.5) & (c < n_in - 0.5)
-    i0 = np.floor(c).astype(np.int64)
-    w = (c - i0).reshape([-1 if d == axis else 1 for d in range(a.ndim)])
-    lo = np.clip(i0, 0, n_in - 1)
-    hi = np.clip(i0 + 1, 0, n_in - 1)
-    out = np.take(a, lo, axis=axis) * (1.0 - w) + np.take(a, hi, axis=axis) * w
-    mask = inside.reshape(w.shape)
-    return np.where(mask, out, 0.0)
-
-
-def _axis_nearest(a: np.ndarray, axis: int, n_out: int) -> np.ndarray:
-    """ITK nearest neighbour along one axis (index rounded half up)."""
-    n_in = a.shape[axis]
-    if n_in == n_out:
-        return a
-    c = np.arange(n_out, dtype=np.float64) * (n_in / n_out)
-    idx = np.floor(c + 0.5).astype(np.int64)
-    inside = idx < n_in
-    out = np.take(a, np.clip(idx, 0, n_in - 1), axis=axis)
-    mask = inside.reshape([-1 if d == axis else 1 for d in range(a.ndim)])
-    return np.where(mask, out, 0)
-
-
-def resample(vol: np.ndarray, target: Tuple[int, int, int], nearest: bool = False) -> np.ndarray:
-    """Resample a (D, H, W) volume to ``target`` with the reference's ResampleImageFilter
-    geometry (script/data_loader.py:258-281 images, linear; :383-406 labels, nearest)."""
-    out = vol.astype(np.float64) if not nearest else vol
-    f = _axis_nearest if nearest else _axis_linear
-    for ax in range(3):
-        out = f(out, ax, int(target[ax]))
-    return out.astype(np.float32)
-
-
-def resample_affine(vol: np.ndarray, target: Tuple[int, int, int], A, t, nearest: bool = False,
-                    gain: float = 1.0, bias: float = 0.0) -> np.ndarray:
-    """``resample`` under a full affine (training-time augmentation): output index (d, h, w)
-    samples source axis a at ``c_a = ((A[a][0]*d + A[a][1]*h) + A[a][2]*w) + t[a]`` -- fp64,
-    every product and sum a numpy operation of its own, in this order.  A gather over the
-    output grid; libpcms_hip's pcms_resample_affine_linear / _label restate it per voxel and
-    are compared with it on the fp32 bits.
-
-    Linear: inside iff ``-0.5 <= c_a < n_a - 0.5`` on all three axes (ITK's buffer rule, as
-    ``_axis_linear``); there ``i0 = floor(c)``, ``w = c - i0``, neighbours ``i0`` and ``i0 + 1``
-    each clamped to ``[0, n - 1]``, the 8 corners lerped ``a*(1-w) + b*w`` along D, then H, then
-    W, rounded once to fp32; unless ``gain == 1 and bias == 0`` an inside voxel then becomes
-    ``fl32(fl32(r*gain) + bias)`` (``gain`` / ``bias`` as fp32).  Outside voxels are 0.
-    ``nearest``: ``k_a = floor(c_a + 0.5)``, 0 where any ``k_a`` is outside ``[0, n_a)``, else the
-    voxel's value as fp32 (the loader binarises it ``> 0``).
-    With ``A = diag(n_in / n_out)``, ``t = 0`` both forms equal ``resample`` bit for bit."""
-    A = np.asarray(A, dtype=np.float64).reshape(3, 3)
-    t = np.asarray(t, dtype=np.float64).reshape(3)
-    D, H, W = (int(v) for v in target)
-    grid = (np.arange(D, dtype=np.float64).reshape(D, 1, 1), np.arange(H, dtype=np.float64).reshape(1, H, 1),
-            np.arange(W, dtype=np.float64).reshape(1, 1, W))
-    with np.errstate(over="ignore", invalid="ignore"):  # a far-out coordinate may overflow: it is outside
-        c = [((A[a, 0] * grid[0] + A[a, 1] * grid[1]) + A[a, 2] * grid[2]) + t[a] for a in range(3)]
-    return _sample_at(vol, c, nearest, gain, bias)
-
-
-def _sample_at(vol: np.ndarray, c, nearest: bool, gain, bias) -> np.ndarray:
-    """The gather of ``resample_affine`` / ``resample_deform`` at the source coordinates ``c``
-    (three fp64 arrays of the output shape): inside rule, clamps, lerp tree, intensity step and
-    nearest rule as ``resample_affine`` documents them."""
-    n_in = vol.shape
-    shape = c[0].shape
-    with np.errstate(over="ignore", invalid="ignore"):
-        if nearest:
-            k = [np.floor(c[a] + 0.5) for a in range(3)]
-            inside = np.ones(shape, dtype=bool)
-            for a in range(3):
-                inside &= (k[a] >= 0.0) & (k[a] < float(n_in[a]))
-            idx = [np.where(inside, k[a], 0.0).astype(np.int64) for a in range(3)]
-            return np.where(inside, vol[idx[0], idx[1], idx[2]], 0).astype(np.float32)
-        inside = np.ones(shape, dtype=bool)
-        for a in range(3):
-            inside &= (c[a] >= -0.5) & (c[a] < n_in[a] - 0.5)
-    lo, hi, w = [], [], []
-    for a in range(3):
-        ca = np.where(inside, c[a], 0.0)
-        i0 = np.floor(ca).astype(np.int64)
-        w.append(ca - i0)
-        lo.append(np.clip(i0, 0, n_in[a] - 1))
-        hi.append(np.clip(i0 + 1, 0, n_in[a] - 1))
-    v = vol.astype(np.float64)
-    vh = []
-    for xw in (lo[2], hi[2]):
-        vd = [v[lo[0], xh, xw] * (1.0 - w[0]) + v[hi[0], xh, xw] * w[0] for xh in (lo[1], hi[1])]
-        vh.append(vd[0] * (1.0 - w[1]) + vd[1] * w[1])
-    out = (vh[0] * (1.0 - w[2]) + vh[1] * w[2]).astype(np.float32)
-    gain, bias = np.float32(gain), np.float32(bias)
-    if not (gain == 1.0 and bias == 0.0):
-        out = out * gain + bias  # two fp32 operations
-    return np.where(inside, out, np.float32(0.0))
-
-
-MAX_CONTROL_POINTS = 512  # gd * gh * gw of an elastic field: 12 KB of doubles in the kernels' LDS
-
-
-def _bspline_axis(n: int, g: int) -> Tuple[np.ndarray, np.ndarray]:
-    """``(k, b)`` of one output axis of extent ``n`` under ``g`` control points: the first of
-    the four control indices per output index and the (n, 4) uniform cubic B-spline weights,
-    one numpy operation per product, sum and division."""
-    x = np.arange(n, dtype=np.float64) * (float(g - 3) / float(n))
-    f = np.floor(x)
-    s = x - f
-    r = 1.0 - s
-    s2 = s * s
-    s3 = s2 * s
-    b0 = ((r * r) * r) / 6.0
-    b1 = ((3.0 * s3 - 6.0 * s2) + 4.0) / 6.0
-    b2 = ((((-3.0 * s3) + 3.0 * s2) + 3.0 * s) + 1.0) / 6.0
-    b3 = s3 / 6.0
-    return f.astype(np.int64), np.stack([b0, b1, b2, b3], axis=1)
-
-
-def field_displacement(field: np.ndarray, target: Tuple[int, int, int]) -> List[np.ndarray]:
-    """The displacement ``[u_D, u_H, u_W]`` (fp64, output voxels, each of shape ``target``) of
-    a control grid ``field[gd][gh][gw][3]``: the uniform cubic B-spline of ``resample_deform``.
-    The inner sums depend on (control row, control row, w), then (control row, h, w), so they
-    are formed once per such triple -- the same operands in the same order as per voxel."""
-    P = np.asarray(field, dtype=np.float64)
-    if P.ndim != 4 or P.shape[3] != 3 or min(P.shape[:3]) < 4:
-        raise ValueError(f"an elastic field is (gd, gh, gw, 3) with every count >= 4, got {P.shape}")
-    D, H, W = (int(v) for v in target)
-    (kd, bd), (kh, bh), (kw, bw) = (_bspline_axis(n, g) for n, g in zip((D, H, W), P.shape[:3]))
-    u = []
-    with np.errstate(over="ignore", invalid="ignore"):  # a non-finite control vector: NaN, outside
-        for c in range(3):
-            Pc = P[..., c]
-            sw = bw[:, 0] * Pc[:, :, kw]                                  # (gd, gh, W)
-            for j in (1, 2, 3):
-                sw = sw + bw[:, j] * Pc[:, :, kw + j]
-            sh = bh[:, 0, None] * sw[:, kh, :]                            # (gd, H, W)
-            for j in (1, 2, 3):
-                sh = sh + bh[:, j, None] * sw[:, kh + j, :]
-            sd = bd[:, 0, None, None] * sh[kd]                            # (D, H, W)
-            for j in (1, 2, 3):
-                sd = sd + bd[:, j, None, None] * sh[kd + j]
-            u.append(sd)
-    return u
-
-
-def resample_deform(vol: np.ndarray, target: Tuple[int, int, int], A, t, field, nearest: bool = False,
-                    gain: float = 1.0, bias: float = 0.0) -> np.ndarray:
-    """``resample_affine`` with a smooth elastic displacement added to the output index before
-    the affine.  ``field`` is one fp64 control grid ``P[gd][gh][gw][3]`` (every count >= 4), a
-    uniform cubic B-spline over the output grid's index space.  For output index ``i`` of an
-    axis of extent ``N`` with ``g`` control points: ``x = i * ((g - 3) / N)``, ``k = floor(x)``
-    (``0 <= k <= g - 4``), ``s = x - k``, ``r = 1 - s``, ``s2 = s*s``, ``s3 = s2*s`` and
-
-        b0 = ((r*r)*r) / 6                     b1 = ((3*s3 - 6*s2) + 4) / 6
-        b2 = ((((-3*s3) + 3*s2) + 3*s) + 1) / 6        b3 = s3 / 6
-
-    ``u_c = sum_jd bd[jd] * (sum_jh bh[jh] * (sum_jw bw[jw] * P[kd+jd][kh+jh][kw+jw][c]))`` for
-    component c in (D, H, W), every sum left to right from j = 0, every product, sum and
-    division a numpy operation of its own.  The voxel samples the source at
-    ``c_a = ((A[a][0]*p_d + A[a][1]*p_h) + A[a][2]*p_w) + t[a]`` with ``p_a = index_a + u_a``;
-    from there on everything is ``resample_affine``'s, and a zero field gives its result bit
-    for bit.  A non-finite control vector gives NaN coordinates, which are outside (0).
-    libpcms_hip's pcms_resample_deform_linear / _label restate this per voxel and are compared
-    with it on the fp32 bits."""
-    A = np.asarray(A, dtype=np.float64).reshape(3, 3)
-    t = np.asarray(t, dtype=np.float64).reshape(3)
-    D, H, W = (int(v) for v in target)
-    u = field_displacement(field, (D, H, W))
-    grid = (np.arange(D, dtype=np.float64).reshape(D, 1, 1), np.arange(H, dtype=np.float64).reshape(1, H, 1),
-            np.arange(W, dtype=np.float64).reshape(1, 1, W))
-    with np.errstate(over="ignore", invalid="ignore"):
-        p = [grid[a] + u[a] for a in range(3)]
-        c = [((A[a, 0] * p[0] + A[a, 1] * p[1]) + A[a, 2] * p[2]) + t[a] for a in range(3)]
-    return _sample_at(vol, c, nearest, gain, bias)
 
 
 @dataclasses.dataclass
@@ -447,191 +121,6 @@ class Augment:
     @property
     def elastic(self) -> bool:
         return any(self.elastic_grid)
-
-
-def _matmul3(a: np.ndarray, b: np.ndarray) -> np.ndarray:
-    """3x3 product with a fixed order of operations (no BLAS: the same doubles everywhere)."""
-    return np.array([[(a[i, 0] * b[0, j] + a[i, 1] * b[1, j]) + a[i, 2] * b[2, j] for j in range(3)] for i in range(3)])
-
-
-def compose_transform(flips=(False, False, False), rotate_deg=(0.0, 0.0, 0.0), zoom: float = 1.0) -> np.ndarray:
-    """The geometric part ``L`` of a transform, in the output grid's index space:
-    ``M = R_D(td) . R_H(th) . R_W(tw)`` (rotations about the D, H and W axes),
-    ``L = F . M^T / zoom`` with ``F = diag(+-1)`` holding the flips."""
-    td, th, tw = (float(np.deg2rad(a)) for a in rotate_deg)
-    c, s = np.cos, np.sin
-    rd = np.array([[1.0, 0.0, 0.0], [0.0, c(td), -s(td)], [0.0, s(td), c(td)]])
-    rh = np.array([[c(th), 0.0, s(th)], [0.0, 1.0, 0.0], [-s(th), 0.0, c(th)]])
-    rw = np.array([[c(tw), -s(tw), 0.0], [s(tw), c(tw), 0.0], [0.0, 0.0, 1.0]])
-    m = _matmul3(_matmul3(rd, rh), rw)
-    f = np.array([-1.0 if b else 1.0 for b in flips])
-    return (f[:, None] * m.T) / float(zoom) + 0.0  # + 0.0: no negative zeros
-
-
-def volume_affine(L, shift, n_in, n_out) -> Tuple[np.ndarray, np.ndarray]:
-    """One volume's ``(A, t)`` of a case's transform: with ``S = diag(n_in / n_out)`` and the
-    output grid's centre ``C = (n_out - 1) / 2``, ``A = S.L`` and ``t = S.(C - L.C - shift)``
-    (``shift`` in output voxels): every volume of a case sees one geometry in output space."""
-    L = np.asarray(L, dtype=np.float64).reshape(3, 3)
-    shift = np.asarray(shift, dtype=np.float64).reshape(3)
-    S = np.array([float(i) / float(o) for i, o in zip(n_in, n_out)])  # numpy's n_in / n_out, as resample
-    C = np.array([(float(o) - 1.0) / 2.0 for o in n_out])
-    LC = np.array([(L[a, 0] * C[0] + L[a, 1] * C[1]) + L[a, 2] * C[2] for a in range(3)])
-    return S[:, None] * L + 0.0, S * ((C - LC) - shift) + 0.0
-
-
-# ---- world geometry: where a file's grid lies in space (DESIGN §0r) -----------------------------
-# A world matrix is 4x4 fp64 and maps a file's (x, y, z) voxel index (homogeneous) to millimetres.
-# Arrays are (z, y, x), so an array-order affine is P . M . P with P the x<->z swap.  All products
-# below are written out (no BLAS): the same doubles wherever they are formed.
-def _matmul4(a: np.ndarray, b: np.ndarray) -> np.ndarray:
-    return np.array([[((a[i, 0] * b[0, j] + a[i, 1] * b[1, j]) + a[i, 2] * b[2, j]) + a[i, 3] * b[3, j]
-                      for j in range(4)] for i in range(4)])
-
-
-def _affine_inverse4(w: np.ndarray, what: str) -> np.ndarray:
-    """The inverse of a 4x4 affine (last row 0 0 0 1) by the adjugate of its 3x3 part; ValueError
-    when that part is singular or not finite."""
-    m = w[:3, :3]
-    c = np.array([[m[(i + 1) % 3, (j + 1) % 3] * m[(i + 2) % 3, (j + 2) % 3]
-                   - m[(i + 1) % 3, (j + 2) % 3] * m[(i + 2) % 3, (j + 1) % 3] for j in range(3)] for i in range(3)])
-    det = (m[0, 0] * c[0, 0] + m[0, 1] * c[0, 1]) + m[0, 2] * c[0, 2]
-    if not np.isfinite(w).all() or det == 0.0:
-        raise ValueError(f"{what}: the world matrix is singular or not finite")
-    inv = np.eye(4)
-    inv[:3, :3] = c.T / det
-    inv[:3, 3] = [-((inv[i, 0] * w[0, 3] + inv[i, 1] * w[1, 3]) + inv[i, 2] * w[2, 3]) for i in range(3)]
-    return inv + 0.0
-
-
-def world_matrix(geometry: dict) -> np.ndarray:
-    """The (4, 4) fp64 matrix that maps a file's (x, y, z) voxel index to millimetres, from a
-    ``read_nifti_geometry`` dict, formed in fp64 from the header's float32 fields.  Precedence:
-    the sform rows (``srow_x/y/z``) when ``sform_code > 0``; else, when ``qform_code > 0``, the
-    NIfTI-1 quaternion form -- ``a = sqrt(1 - b^2 - c^2 - d^2)`` (0 when the sum exceeds 1), the
-    rotation of (a, b, c, d), its columns scaled by ``pixdim[1..3]``, the third also by ``qfac =
-    pixdim[0]`` (-1 only when the field is exactly -1, else +1), the offset ``qoffset_x/y/z``;
-    else ``diag(pixdim[1..3])`` with a zero offset."""
-    g = geometry
-    w = np.eye(4)
-    pix = [float(v) for v in g["pixdim"]]
-    if int(g["sform_code"]) > 0:
-        for i, name in enumerate(("srow_x", "srow_y", "srow_z")):
-            w[i, :] = [float(v) for v in g[name]]
-        return w
-    if int(g["qform_code"]) > 0:
-        b, c, d = float(g["quatern_b"]), float(g["quatern_c"]), float(g["quatern_d"])
-        a2 = 1.0 - (b * b + c * c + d * d)
-        a = float(np.sqrt(a2)) if a2 > 0.0 else 0.0
-        r = np.array([[a * a + b * b - c * c - d * d, 2.0 * (b * c - a * d), 2.0 * (b * d + a * c)],
-                      [2.0 * (b * c + a * d), a * a + c * c - b * b - d * d, 2.0 * (c * d - a * b)],
-                      [2.0 * (b * d - a * c), 2.0 * (c * d + a * b), a * a + d * d - b * b - c * c]])
-        qfac = -1.0 if pix[0] == -1.0 else 1.0
-        w[:3, :3] = r * np.array([pix[1], pix[2], pix[3] * qfac])
-        w[:3, 3] = [float(g["qoffset_x"]), float(g["qoffset_y"]), float(g["qoffset_z"])]
-        return w + 0.0
-    w[0, 0], w[1, 1], w[2, 2] = pix[1], pix[2], pix[3]
-    return w
-
-
-RIGID_NAMES = ("tz", "ty", "tx", "rz", "ry", "rx")  # millimetres, then degrees
-
-
-def rigid_world(params, centre_xyz) -> np.ndarray:
-    """The (4, 4) rigid motion of six parameters ``(tz, ty, tx mm; rz, ry, rx degrees)`` in world
-    millimetres about the world point ``centre_xyz``: ``x -> R (x - c) + c + (tx, ty, tz)`` with
-    ``R = R_z(rz) . R_y(ry) . R_x(rx)``, each a right-handed rotation about that world axis."""
-    tz, ty, tx, rz, ry, rx = (float(v) for v in params)
-    az, ay, ax = (float(np.deg2rad(v)) for v in (rz, ry, rx))
-    c, s = np.cos, np.sin
-    mz = np.array([[c(az), -s(az), 0.0], [s(az), c(az), 0.0], [0.0, 0.0, 1.0]])
-    my = np.array([[c(ay), 0.0, s(ay)], [0.0, 1.0, 0.0], [-s(ay), 0.0, c(ay)]])
-    mx = np.array([[1.0, 0.0, 0.0], [0.0, c(ax), -s(ax)], [0.0, s(ax), c(ax)]])
-    r = _matmul3(_matmul3(mz, my), mx)
-    cen = np.asarray(centre_xyz, dtype=np.float64).reshape(3)
-    rc = np.array([(r[i, 0] * cen[0] + r[i, 1] * cen[1]) + r[i, 2] * cen[2] for i in range(3)])
-    m = np.eye(4)
-    m[:3, :3] = r
-    m[:3, 3] = (cen - rc) + np.array([tx, ty, tz])
-    return m + 0.0
-
-
-def world_centre(geometry: dict, shape_zyx) -> np.ndarray:
-    """The world position (x, y, z mm) of the centre ``(n - 1) / 2`` of a (z, y, x) grid."""
-    w = world_matrix(geometry)
-    i = np.array([(float(n) - 1.0) / 2.0 for n in tuple(shape_zyx)[::-1]])
-    return np.array([((w[a, 0] * i[0] + w[a, 1] * i[1]) + w[a, 2] * i[2]) + w[a, 3] for a in range(3)])
-
-
-def rigid_correction(params, ref_geometry: dict, ref_shape) -> np.ndarray:
-    """``rigid_world`` of ``params`` about the centre of the reference grid: the ``correction``
-    ``align_affine`` takes for a ``predict.register_rigid`` result."""
-    return rigid_world(params, world_centre(ref_geometry, ref_shape))
-
-
-def align_affine(ref_geometry: dict, mov_geometry: dict, correction=None) -> Tuple[np.ndarray, np.ndarray]:
-    """``(A, t)`` in array order (z, y, x) that takes an array index of the reference file to the
-    array index of the same world point in the moving file: ``P . inv(W_mov) . [T] . W_ref . P``
-    with ``W`` the ``world_matrix`` of each file, ``P`` the x<->z swap and ``T`` an optional (4, 4)
-    rigid ``correction`` in world millimetres (``rigid_correction``: reference world -> moving
-    world).  A singular ``W_mov`` raises ValueError.  Without a correction and with two world
-    matrices equal element for element the result is exactly ``(I, 0)``.  A reference voxel whose
-    image lies outside the moving grid reads 0 in every resampler (the outside rule of
-    ``resample_affine``)."""
-    w_ref, w_mov = world_matrix(ref_geometry), world_matrix(mov_geometry)
-    inv = _affine_inverse4(w_mov, "align_affine")
-    if correction is None and np.array_equal(w_ref, w_mov):
-        return np.eye(3), np.zeros(3)
-    m = w_ref
-    if correction is not None:
-        T = np.asarray(correction, dtype=np.float64)
-        if T.shape != (4, 4) or not np.isfinite(T).all():
-            raise ValueError(f"correction is a finite (4, 4) matrix, got {correction!r}")
-        m = _matmul4(T, m)
-    m = _matmul4(inv, m)
-    return m[:3, :3][::-1, ::-1] + 0.0, m[:3, 3][::-1] + 0.0
-
-
-def compose_affine(first, second) -> Tuple[np.ndarray, np.ndarray]:
-    """``(A, t)`` of ``x -> second(first(x))`` for two ``(A, t)`` pairs, in fp64 with every product
-    and sum written out: ``A = A2 . A1``, ``t = A2 . t1 + t2``.  An identity ``second`` gives
-    ``first`` back exactly."""
-    A1, t1 = np.asarray(first[0], dtype=np.float64).reshape(3, 3), np.asarray(first[1], dtype=np.float64).reshape(3)
-    A2, t2 = np.asarray(second[0], dtype=np.float64).reshape(3, 3), np.asarray(second[1], dtype=np.float64).reshape(3)
-    A = _matmul3(A2, A1)
-    t = np.array([((A2[i, 0] * t1[0] + A2[i, 1] * t1[1]) + A2[i, 2] * t1[2]) + t2[i] for i in range(3)])
-    return A + 0.0, t + 0.0
-
-
-def case_affine(L, shift, n_in, n_out, alignment=None) -> Tuple[np.ndarray, np.ndarray]:
-    """One volume's ``(A, t)`` from the case grid ``n_out`` into the volume's own array: the one
-    function every loader, host or device, forms it with.  Without ``alignment`` it is
-    ``volume_affine(L, shift, n_in, n_out)``: the file stretched onto the grid.  ``alignment`` is
-    ``(ref_shape, (A, t))``: the case grid is scaled onto the reference file's native grid
-    (``volume_affine`` with the reference's shape) and that is composed with the ``align_affine``
-    pair into this volume; ``n_in`` then plays no part."""
-    if alignment is None:
-        return volume_affine(L, shift, n_in, n_out)
-    ref_shape, pair = alignment
-    return compose_affine(volume_affine(L, shift, tuple(int(v) for v in ref_shape), n_out), pair)
-
-
-def affine12_of(A, t) -> Tuple[float, ...]:
-    """``(A, t)`` as the twelve doubles the C entry points take: row-major A, then t."""
-    return tuple(float(v) for v in np.asarray(A).reshape(-1)) + tuple(float(v) for v in np.asarray(t).reshape(-1))
-
-
-def registration_fixed(modalities: Sequence[str], present, to: Optional[str]) -> str:
-    """The modality the others of a case are registered to, and about whose centre their rigid
-    corrections turn: ``to`` when it names a present modality, else the first present one in
-    ``modalities`` order (a label or any other file only lends its grid)."""
-    if to in modalities and to in present:
-        return to
-    return next(m for m in modalities if m in present)
-
-
-def _shape_zyx(path: str) -> Tuple[int, int, int]:
-    return tuple(int(v) for v in read_nifti_header(path)["shape_xyz"][:3][::-1])
 
 
 @dataclasses.dataclass
@@ -697,17 +186,9 @@ def draw_transform(aug, seed: int, epoch: int, case_number: int,
 
 # ---- patch training: foreground-biased crops of the window's shape ---------------------------
 MAX_PATCHES = 64        # patches per case: one workgroup of the pick each, one launch per modality
+
+
 MAX_PATCH_AXIS = 512    # the label patches come out of pcms_window_gather, which caps a window axis
-
-
-def _axes3(v, what: str) -> Tuple[int, int, int]:
-    try:
-        out = tuple(v)
-    except TypeError:
-        raise ValueError(f"{what} is three integers (d, h, w), got {v!r}") from None
-    if len(out) != 3 or any(isinstance(a, bool) or int(a) != a for a in out):
-        raise ValueError(f"{what} is three integers (d, h, w), got {v!r}")
-    return tuple(int(a) for a in out)
 
 
 @dataclasses.dataclass
@@ -719,7 +200,7 @@ class PatchSampling:
     file).  A share ``foreground_prob`` of them is centred on a lesion voxel (``draw_patches``,
     ``pick_origins``).  ``normalise``: every modality is normalised over its whole volume first, as
     ``predict.prepare_case`` does: ``True`` is min-max (and stays ``True``); a method name
-    (``"percentile"``), a dict or a ``predict.Normalisation`` is kept as a ``Normalisation``.
+    (``"percentile"``), a dict or an ``intensity.Normalisation`` is kept as a ``Normalisation``.
     ``seed`` seeds the patch draws."""
     patch_size: Tuple[int, int, int] = (16, 128, 128)
     patches_per_case: int = 2
@@ -735,7 +216,7 @@ class PatchSampling:
         return PatchSampling(**dict(patches))
 
     def __post_init__(self):
-        self.patch_size = _axes3(self.patch_size, "PatchSampling.patch_size")
+        self.patch_size = axes3(self.patch_size, "PatchSampling.patch_size")
         if any(w < 16 or w % 16 or w > MAX_PATCH_AXIS for w in self.patch_size):
             raise ValueError("PatchSampling.patch_size: every axis is a multiple of 16 (the network pools four "
                              f"times) up to {MAX_PATCH_AXIS}, got {self.patch_size}")
@@ -747,11 +228,10 @@ class PatchSampling:
         if not 0.0 <= self.foreground_prob <= 1.0:  # false for NaN
             raise ValueError(f"PatchSampling.foreground_prob lies in [0, 1], got {self.foreground_prob!r}")
         if self.grid is not None:
-            self.grid = _axes3(self.grid, "PatchSampling.grid")
+            self.grid = axes3(self.grid, "PatchSampling.grid")
             if min(self.grid) < 1:
                 raise ValueError(f"PatchSampling.grid: every axis is at least 1, got {self.grid}")
         if isinstance(self.normalise, (str, dict)) or dataclasses.is_dataclass(self.normalise):
-            from .predict import Normalisation
             self.normalise = Normalisation.of(self.normalise)  # ValueError for an unknown method
         else:
             self.normalise = bool(self.normalise)
@@ -761,7 +241,7 @@ class PatchSampling:
 def _resample_patch(vol: np.ndarray, grid, A, t, origin, patch, gain, bias) -> np.ndarray:
     A = np.asarray(A, dtype=np.float64).reshape(3, 3)
     t = np.asarray(t, dtype=np.float64).reshape(3)
-    grid, patch, origin = _axes3(grid, "grid"), _axes3(patch, "patch"), _axes3(origin, "origin")
+    grid, patch, origin = axes3(grid, "grid"), axes3(patch, "patch"), axes3(origin, "origin")
     shapes = ((-1, 1, 1), (1, -1, 1), (1, 1, -1))
     idx = [(np.arange(w, dtype=np.int64) + o).reshape(s) for w, o, s in zip(patch, origin, shapes)]
     p = [i.astype(np.float64) for i in idx]
@@ -782,13 +262,12 @@ def resample_patch(vol: np.ndarray, grid, A, t, origin, patch, gain: float = 1.0
     samples the source at ``c_a = ((A[a][0]*p_d + A[a][1]*p_h) + A[a][2]*p_w) + t[a]``; from the
     coordinate on everything is ``resample_affine``'s (``_sample_at``).  The result is 0 where any
     ``p_a < 0`` or ``p_a >= grid[a]``: a patch that sticks out of the grid is zero-padded, as
-    ``predict.gather_windows`` pads a window.  ``normalise``: ``vol`` is first replaced by
-    ``predict.normalise(vol)`` (min-max over the whole volume, the corner rule of
-    pcms_resample_linear_norm); anything else ``predict.Normalisation.of`` accepts selects that
-    normalisation (``"percentile"``: ``predict.normalise_window`` at the volume's
-    ``predict.intensity_window``).  libpcms_hip's pcms_patch_resample_linear and
+    ``window.gather_windows`` pads a window.  ``normalise``: ``vol`` is first replaced by
+    ``intensity.normalise(vol)`` (min-max over the whole volume, the corner rule of
+    pcms_resample_linear_norm); anything else ``intensity.Normalisation.of`` accepts selects that
+    normalisation (``"percentile"``: ``intensity.normalise_window`` at the volume's
+    ``intensity.intensity_window``).  libpcms_hip's pcms_patch_resample_linear and
     pcms_patch_resample_window restate this per voxel and are compared with it on the fp32 bits."""
-    from .predict import Normalisation
     norm = Normalisation.of(normalise)
     if norm is not None:
         vol = norm.apply(vol)
@@ -811,7 +290,7 @@ def draw_patches(sampling, seed: int, epoch: int, case_number: int, grid=None) -
     grid = sampling.grid if sampling.grid is not None else grid
     if grid is None:
         raise ValueError("draw_patches needs the case grid: PatchSampling.grid is None and no grid was given")
-    grid = _axes3(grid, "grid")
+    grid = axes3(grid, "grid")
     rng = np.random.default_rng([int(seed), int(epoch), int(case_number), 1])
     P = sampling.patches_per_case
     rank_u = np.empty(P, dtype=np.float64)
@@ -839,7 +318,7 @@ def pick_origins(label_grid: np.ndarray, patch, rank_u, fallback) -> Tuple[np.nd
     lab = np.asarray(label_grid)
     if lab.ndim != 3 or 0 in lab.shape:
         raise ValueError(f"pick_origins takes a non-empty (D, H, W) label grid, got shape {lab.shape}")
-    patch = _axes3(patch, "patch")
+    patch = axes3(patch, "patch")
     if min(patch) < 1:
         raise ValueError(f"a patch axis is at least 1, got {patch}")
     rank_u = np.asarray(rank_u, dtype=np.float64).reshape(-1)
@@ -861,67 +340,6 @@ def pick_origins(label_grid: np.ndarray, patch, rank_u, fallback) -> Tuple[np.nd
         v = np.unravel_index(int(fg[r]), G)
         origins[i] = [min(max(int(v[a]) - patch[a] // 2, 0), top[a]) for a in range(3)]
     return origins, T
-
-
-def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool = False,
-                    out: Optional[torch.Tensor] = None, affine: Optional[Sequence[float]] = None,
-                    gain: float = 1.0, bias: float = 0.0, field: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``resample`` of a volume whose bytes are on the GPU, on the current stream: the linear
-    form equals ``resample(vol.astype(float32), target)`` bit for bit, ``nearest=True`` gives
-    the binarised label ``resample(vol, target, nearest=True) > 0`` as fp32 {0, 1} (for a
-    volume already of the target shape, ``vol > 0``), as ``ProstateDataset.__getitem__`` forms
-    them.  Fills ``out`` (a contiguous fp32 (D, H, W) device tensor, e.g. one channel of a
-    batch) or returns a new one.  There is no CPU form: host bytes raise.
-    ``affine`` (twelve doubles, row-major A then t) selects the augmenting entry points:
-    ``resample_affine(vol.astype(float32), target, A, t, gain=gain, bias=bias)`` and, with
-    ``nearest``, ``resample_affine(vol, target, A, t, nearest=True) > 0``, bit for bit.
-    ``field`` (a contiguous fp64 ``(gd, gh, gw, 3)`` tensor on the volume's device; needs
-    ``affine``) selects the deforming entry points: ``resample_deform`` with that control grid
-    in place of ``resample_affine``, bit for bit again."""
-    from ._lib import call
-    target = tuple(int(v) for v in target)
-    if raw.data.device.type != "cuda":
-        raise RuntimeError("resample_device needs the volume's bytes on a GPU (RawVolume.to(device)); "
-                           "pcms_amd has no CPU fallback -- use data.resample on the host")
-    if raw.data.dtype != torch.uint8 or not raw.data.is_contiguous():
-        raise ValueError("RawVolume.data must be a contiguous uint8 tensor")
-    itemsize = np.dtype(_NIFTI_DTYPES[raw.code]).itemsize
-    if raw.data.numel() != int(np.prod(raw.shape)) * itemsize:
-        raise ValueError(f"RawVolume holds {raw.data.numel()} bytes, shape {raw.shape} of datatype {raw.code} "
-                         f"needs {int(np.prod(raw.shape)) * itemsize}")
-    if out is None:
-        out = torch.empty(target, dtype=torch.float32, device=raw.data.device)
-    elif (tuple(out.shape) != target or out.dtype != torch.float32 or not out.is_contiguous()
-          or out.device != raw.data.device):
-        raise ValueError(f"out must be a contiguous fp32 {target} tensor on {raw.data.device}")
-    if affine is None:
-        if field is not None:
-            raise ValueError("field needs affine: the deformation is applied in front of the affine")
-        call("pcms_resample_label" if nearest else "pcms_resample_linear", raw.data, int(raw.code), *raw.shape,
-             float(raw.slope), float(raw.inter), out, *target)
-        return out
-    if len(affine) != 12:
-        raise ValueError("affine must hold twelve doubles: row-major A[3][3], then t[3]")
-    host = (ctypes.c_double * 12)(*(float(v) for v in affine))  # read during the call (kernel arguments)
-    if field is not None:
-        if (field.dtype != torch.float64 or field.dim() != 4 or field.shape[3] != 3 or not field.is_contiguous()
-                or field.device != raw.data.device):
-            raise ValueError(f"field must be a contiguous fp64 (gd, gh, gw, 3) tensor on {raw.data.device}")
-        grid = tuple(int(v) for v in field.shape[:3])
-        if nearest:
-            call("pcms_resample_deform_label", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
-                 ctypes.addressof(host), field, *grid, out, *target)
-        else:
-            call("pcms_resample_deform_linear", raw.data, int(raw.code), *raw.shape, float(raw.slope),
-                 float(raw.inter), ctypes.addressof(host), field, *grid, float(gain), float(bias), out, *target)
-        return out
-    if nearest:
-        call("pcms_resample_affine_label", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
-             ctypes.addressof(host), out, *target)
-    else:
-        call("pcms_resample_affine_linear", raw.data, int(raw.code), *raw.shape, float(raw.slope), float(raw.inter),
-             ctypes.addressof(host), float(gain), float(bias), out, *target)
-    return out
 
 
 def is_raw_batch(batch) -> bool:
@@ -980,20 +398,18 @@ def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
     batch's ``"normalise"`` entry selects the percentile window; ``None`` channels are zeroed),
     and one pcms_window_gather cuts the label patches.  Everything is enqueued on the current
     stream, with no host synchronisation."""
-    from ._lib import call, query
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError(f"a device_resample batch can only be assembled on a GPU, not on '{device}': "
                            "pcms_amd has no CPU resampling kernel (use the default loader there)")
     images, labels, draws = raw_batch["raw_images"], raw_batch["raw_label"], raw_batch["patches"]
     patch = tuple(int(v) for v in raw_batch["patch_size"])
-    from .predict import Normalisation, _lohi_enqueue
     norm = Normalisation.of(raw_batch["normalise"])
     normalise = norm is not None
     n, m = len(images), len(images[0])
     P = int(draws[0]["rank_u"].numel())
     nwin = patch[0] * patch[1] * patch[2]
-    no_flip = (ctypes.c_int * 1)(0)  # read during the call (kernel arguments)
+    no_flip = host_ints([0])  # read during the calls: stays in this local until the last one returns
     with torch.cuda.device(device):
         image = torch.empty((n * P, m) + patch, dtype=torch.float32, device=device)
         label = torch.empty((n * P, 1) + patch, dtype=torch.float32, device=device)
@@ -1020,16 +436,13 @@ def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
                     image[i * P:(i + 1) * P, c].zero_()
                     continue
                 raw = raw if raw.data.device.type == "cuda" else raw.pin_memory().to(device, True)
-                cnt = int(np.prod(raw.shape))
-                if raw.data.dtype != torch.uint8 or raw.data.numel() != cnt * np.dtype(_NIFTI_DTYPES[raw.code]).itemsize:
-                    raise ValueError(f"RawVolume holds {raw.data.numel()} bytes, shape {raw.shape} of datatype "
-                                     f"{raw.code} needs {cnt * np.dtype(_NIFTI_DTYPES[raw.code]).itemsize}")
+                raw = device_raw(raw, "assemble_patch_batch")
                 # the window is formed once per volume and read from device memory by every patch
                 windowed = normalise and _lohi_enqueue(raw, norm, lohi) == "window"
-                host = (ctypes.c_double * 12)(*(float(v) for v in d["affine"][c]))  # read during the call
-                call("pcms_patch_resample_window" if windowed else "pcms_patch_resample_linear", raw.data,
-                     int(raw.code), *raw.shape, float(raw.slope), float(raw.inter), ctypes.addressof(host), lohi,
-                     float(d["gain"][c]), float(d["bias"][c]), *grid, picks[i], P, first, m * nwin, *patch)
+                host = host_affine12(d["affine"][c])  # read during the call: stays in this local until it returns
+                call("pcms_patch_resample_window" if windowed else "pcms_patch_resample_linear", *raw.kernel_args(),
+                     ctypes.addressof(host), lohi, float(d["gain"][c]), float(d["bias"][c]), *grid, picks[i], P, first,
+                     m * nwin, *patch)
             call("pcms_window_gather", label_grid, 1, *grid, picks[i], P, ctypes.addressof(no_flip), 1, *patch,
                  label[i * P:(i + 1) * P])
     return {"image": image, "label": label, "case_id": [cid for cid in raw_batch["case_id"] for _ in range(P)],
@@ -1095,7 +508,7 @@ class ProstateDataset(Dataset):
         the case grid under that transform (the identity draw without ``augment``) at origins
         drawn by ``draw_patches`` / ``pick_origins``; ``target_size`` is unused, ``set_epoch``
         moves the patch draws too, and an elastic ``augment`` is not supported with it.
-        ``align`` (anything ``predict.Alignment.of`` accepts; None: off, every sample as before):
+        ``align`` (anything ``align.Alignment.of`` accepts; None: off, every sample as before):
         every volume of a case, the label included, is placed on the grid of the reference file
         through its NIfTI world geometry (``case_affine``: the case grid scaled onto the
         reference's native grid, then ``align_affine`` into the volume's file) instead of being
@@ -1103,7 +516,7 @@ class ProstateDataset(Dataset):
         ``align.to``: ``"label"`` (the default: the label file, whose own map is then the
         identity) or a modality name; with ``patches`` a ``grid`` of None is its shape.  It
         composes with ``augment``, ``patches`` and ``device_resample``, and both kinds of loader
-        give the same batches.  ``corrections`` (``predict.register_dataset``'s dict ``{case_id:
+        give the same batches.  ``corrections`` (``align.register_dataset``'s dict ``{case_id:
         {modality: six parameters}}`` or the path of its JSON; needs ``align``): the rigid
         correction of each modality goes into its map.  Training never registers on the fly:
         ``mode="register"`` without ``corrections`` raises."""
@@ -1114,10 +527,7 @@ class ProstateDataset(Dataset):
         if self.patches is not None and self.augment is not None and self.augment.elastic:
             raise ValueError("patches and Augment.elastic_grid cannot be combined: the patch resampler has no "
                              "deforming form")
-        self.align = None
-        if align is not None:
-            from .predict import Alignment
-            self.align = Alignment.of(align)
+        self.align = Alignment.of(align)
         if isinstance(corrections, (str, os.PathLike)):
             import json
             with open(corrections) as f:
@@ -1271,7 +681,7 @@ class ProstateDataset(Dataset):
         ``augment``) maps every volume onto the case grid; the label is formed on the whole grid
         (``resample_affine(..., nearest=True) > 0``), the origins are picked on it, each modality
         is sampled at the patches' coordinates alone (``resample_patch``) and the label patches
-        are ``predict.gather_windows`` of the grid label.  ``device_resample``: the volumes are
+        are ``window.gather_windows`` of the grid label.  ``device_resample``: the volumes are
         handed over undecoded with the twelve doubles per volume and the patch draws as CPU
         tensors, and ``assemble_patch_batch`` does all of that on the GPU."""
         case = self.case_list[idx]
@@ -1292,7 +702,6 @@ class ProstateDataset(Dataset):
                      # CPU tensors, so that the DataLoader's pin_memory handles them
                      "rank_u": torch.from_numpy(rank_u), "fallback": torch.from_numpy(fallback)}
             return {"raw_images": raws, "raw_label": lab, "case_id": case["case_id"], "patches": draws}
-        from .predict import Normalisation, gather_windows
         lab = self._first_volume(read_nifti(case["label_path"]))
         grid = ps.grid if ps.grid is not None else tuple(lab.shape) if al is None else al["label"][0]
         rank_u, fallback = draw_patches(ps, ps.seed, self.epoch, idx, grid)

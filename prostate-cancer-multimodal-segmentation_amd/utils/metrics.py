@@ -16,7 +16,8 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import numpy as np
 import torch
 
-from ..data import device_batch
+from .. import distance, lesions
+from ..data import device_batch, get_dataloader
 
 
 def calculate_dice_score(pred: torch.Tensor, target: torch.Tensor) -> float:
@@ -48,15 +49,14 @@ def calculate_surface_metrics(pred, target, spacing: Sequence[float] = (1.0, 1.0
     """Boundary metrics of two binary masks (foreground ``!= 0``) in the units of ``spacing =
     (sz, sy, sx)``: ``hd`` (Hausdorff distance), ``hd95`` (its 95th percentile, MedPy's), ``assd``
     (average symmetric surface distance), ``n_a`` / ``n_b`` (surface voxels of pred / target).
-    CUDA tensors are scored on the device (predict.surface_metrics_device: exact distance
-    transform in HIP), numpy arrays by the host form (predict.surface_metrics); a CPU tensor
+    CUDA tensors are scored on the device (distance.surface_metrics_device: exact distance
+    transform in HIP), numpy arrays by the host form (distance.surface_metrics); a CPU tensor
     raises, as everywhere in pcms_amd.  Both surfaces empty: 0.0; exactly one empty: inf."""
-    from .. import predict
     if isinstance(pred, np.ndarray) and isinstance(target, np.ndarray):
-        return predict.surface_metrics(_as_volume(pred), _as_volume(target), spacing)
+        return distance.surface_metrics(_as_volume(pred), _as_volume(target), spacing)
     if isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor):
         p, t = ((_as_volume(m) != 0).to(torch.uint8) if m.device.type == "cuda" else m for m in (pred, target))
-        return predict.surface_metrics_device(p, t, spacing)
+        return distance.surface_metrics_device(p, t, spacing)
     raise TypeError("pred and target are both CUDA tensors or both numpy arrays, got "
                     f"{type(pred).__name__} and {type(target).__name__}")
 
@@ -64,16 +64,15 @@ def calculate_surface_metrics(pred, target, spacing: Sequence[float] = (1.0, 1.0
 def calculate_lesion_metrics(pred, target, spacing: Sequence[float] = (1.0, 1.0, 1.0), connectivity: int = 26,
                              min_iou: float = 0.1) -> Dict:
     """Lesion-level detection scores of two binary masks (foreground ``!= 0``): connected
-    components at ``connectivity`` matched one to one at ``min_iou`` (predict.lesion_metrics has
+    components at ``connectivity`` matched one to one at ``min_iou`` (lesions.lesion_metrics has
     the definition and the keys: ``tp`` / ``fp`` / ``fn`` / ``sensitivity`` / ``precision`` / ``f1``
     and the per-lesion tables).  CUDA tensors are scored on the device
-    (predict.lesion_metrics_device), numpy arrays by the host form; a CPU tensor raises."""
-    from .. import predict
+    (lesions.lesion_metrics_device), numpy arrays by the host form; a CPU tensor raises."""
     if isinstance(pred, np.ndarray) and isinstance(target, np.ndarray):
-        return predict.lesion_metrics(_as_volume(pred), _as_volume(target), None, spacing, connectivity, min_iou)
+        return lesions.lesion_metrics(_as_volume(pred), _as_volume(target), None, spacing, connectivity, min_iou)
     if isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor):
         p, t = ((_as_volume(m) != 0).to(torch.uint8) if m.device.type == "cuda" else m for m in (pred, target))
-        return predict.lesion_metrics_device(p, t, None, spacing, connectivity, min_iou)
+        return lesions.lesion_metrics_device(p, t, None, spacing, connectivity, min_iou)
     raise TypeError("pred and target are both CUDA tensors or both numpy arrays, got "
                     f"{type(pred).__name__} and {type(target).__name__}")
 
@@ -157,7 +156,6 @@ class ModelValidator:
         self.model = model
         self.model.eval()
         if test_loader is None and config.get("data_dir"):
-            from ..data import get_dataloader
             test_loader = get_dataloader(config["data_dir"], batch_size=config.get("batch_size", 1), shuffle=False,
                                          missing_strategy=config.get("handle_missing_modalities", "zero_fill"),
                                          target_size=tuple(config.get("target_size", (128, 128, 128))),

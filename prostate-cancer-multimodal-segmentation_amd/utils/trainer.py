@@ -30,8 +30,8 @@ case and epoch; validation never augments; both loaders give the same batches), 
 sliding-window predictor's window shape, a step sees ``batch_size * P`` of them; the validation
 loader cuts patches too, without augmentation and at epoch 0, so the same ones every epoch --
 whole-case sliding-window validation is not part of the trainer), ``align`` / ``corrections``
-(``predict.Alignment``: every volume of a case is placed on the reference file's grid through its
-NIfTI world geometry, with the rigid corrections of ``predict.register_dataset`` -- a dict or the
+(``align.Alignment``: every volume of a case is placed on the reference file's grid through its
+NIfTI world geometry, with the rigid corrections of ``align.register_dataset`` -- a dict or the
 path of its JSON -- when given; training never registers on the fly), and the step
 variants of the other reference trainers:
   ``max_grad_norm``  clip_grad_norm_(max_norm) before Adam (train_bph.py:166,

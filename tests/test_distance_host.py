@@ -161,29 +161,31 @@ def test_surface_metrics_by_hand():
 
 def test_hd95_interpolates_between_order_statistics():
     predict = _predict()
+    from pcms_amd import distance
     # n = 12: pos = 11 * 0.95 = 10.45, between v[10] and v[11]
     v = np.array([0.5 * k * k for k in range(12)])
     pos = 11 * 0.95
     assert pos != math.floor(pos) and math.floor(pos) == 10
     exp = v[10] + (v[11] - v[10]) * (pos - 10)
-    assert predict._percentile95(v) == exp and v[10] < exp < v[11]
-    assert predict._percentile95(np.array([7.0])) == 7.0
+    assert distance._percentile95(v) == exp and v[10] < exp < v[11]
+    assert distance._percentile95(np.array([7.0])) == 7.0
     # n = 21: pos = 19 exactly -- the order statistic itself
     w = np.arange(21, dtype=np.float64) ** 1.5
-    assert predict._percentile95(w) == w[19]
+    assert distance._percentile95(w) == w[19]
     # through surface_metrics: a line of 6 voxels against one voxel at its end; da = 0..5, db = [0]
     a, b = np.zeros((1, 1, 9), np.uint8), np.zeros((1, 1, 9), np.uint8)
     a[0, 0, :6] = 1
     b[0, 0, 0] = 1
     m = predict.surface_metrics(a, b, (1.0, 1.0, 0.7))
     both = np.sort(np.array([0.0] + [math.sqrt((k * 0.7) * (k * 0.7)) for k in range(6)]))
-    assert m["hd95"] == predict._percentile95(both) and m["hd"] == both[-1]
+    assert m["hd95"] == distance._percentile95(both) and m["hd"] == both[-1]
     assert m["assd"] == (float(both[1:].mean()) + 0.0) / 2.0
 
 
 def test_against_scipy_and_numpy():
     ndi = pytest.importorskip("scipy.ndimage")
     predict = _predict()
+    from pcms_amd import distance
     compared = 0
     for shape in SHAPES[1:] + [(6, 20, 18)]:
         for kind in ("single", "bernoulli0.02", "bernoulli0.3", "full"):
@@ -202,7 +204,7 @@ def test_against_scipy_and_numpy():
     rng = np.random.default_rng(5)
     for n in (1, 2, 12, 21, 1000):
         v = np.sort(rng.random(n) * 40.0)
-        assert abs(predict._percentile95(v) - np.percentile(v, 95)) <= 1e-12 * np.percentile(v, 95)
+        assert abs(distance._percentile95(v) - np.percentile(v, 95)) <= 1e-12 * np.percentile(v, 95)
     # the whole chain against MedPy's recipe
     a = np.zeros((6, 20, 18), np.uint8)
     b = np.zeros_like(a)

@@ -92,7 +92,7 @@ def main():
     ap.add_argument("--case-reps", type=int, default=3)
     a = ap.parse_args()
     import pcms_amd  # noqa: F401
-    from pcms_amd import data, predict
+    from pcms_amd import align, data, intensity, predict
     device = torch.device("cuda", 0)
     root = tempfile.mkdtemp(prefix="align_time_")
     vols, gf, gm = make_case(root, data)
@@ -110,15 +110,15 @@ def main():
 
     sets = []
     for _ in range(3):
-        s = {"fix": raw(fix), "mov": raw(mov), "work": predict._joint_work(bins, device)}
-        s["fl"], s["ml"] = predict._window_device(s["fix"], None), predict._window_device(s["mov"], None)
+        s = {"fix": raw(fix), "mov": raw(mov), "work": align._joint_work(bins, device)}
+        s["fl"], s["ml"] = intensity._window_device(s["fix"], None), intensity._window_device(s["mov"], None)
         sets.append(s)
     strides = {"stride_1_1_1": (1, 1, 1), "stride_1_2_2": (1, 2, 2)}
-    calls = {k: (lambda s, st=st: predict._joint_enqueue(s["fix"], s["mov"], A, t, s["fl"], s["ml"], bins, st, s["work"]))
+    calls = {k: (lambda s, st=st: align._joint_enqueue(s["fix"], s["mov"], A, t, s["fl"], s["ml"], bins, st, s["work"]))
              for k, st in strides.items()}
     for k, st in strides.items():
         got = calls[k](sets[0]).cpu().numpy().astype(np.int64)
-        exp = predict.joint_histogram(fix, mov, A, t, predict._host_lohi(fix, None), predict._host_lohi(mov, None), bins, st)
+        exp = predict.joint_histogram(fix, mov, A, t, intensity._host_lohi(fix, None), intensity._host_lohi(mov, None), bins, st)
         assert np.array_equal(got, exp), (k, int(got.sum()), int(exp.sum()))
         lattice = int(np.prod([-(-n // s) for n, s in zip(FIX_SHAPE, st)]))
         fetched = FIX_SHAPE[0] // st[0] * -(-FIX_SHAPE[1] // st[1]) * FIX_SHAPE[2] * 2 + int(np.prod(MOV_SHAPE)) * 2

@@ -46,6 +46,7 @@ def table_bytes(table, header):
 
 def device_times(L, predict, cases, device, reps, iters):
     """cases: name -> (labels, prob or None, host table)."""
+    from pcms_amd import lesions
     nwork = L.query("pcms_component_table_work_bytes", *RAW_SHAPE)
     out = {}
     for name, (lab, prob, host) in cases.items():
@@ -66,7 +67,7 @@ def device_times(L, predict, cases, device, reps, iters):
         assert all(np.array_equal(r, raws[0]) for r in raws), name
         status, K = (int(v) for v in raws[0][-8:].view(np.int32))
         assert status == 0 and K == len(host["label"]) <= CAPACITY, name
-        got = predict._table_columns(raws[0][:-8], CAPACITY, K, prob is not None)
+        got = lesions._table_columns(raws[0][:-8], CAPACITY, K, prob is not None)
         assert all(np.array_equal(got[k].view(np.uint8), host[k].view(np.uint8)) for k in host), name
         windows = []
         for _ in range(reps):
