@@ -367,6 +367,39 @@ int pcms_loss_fwd(const float* x, const float* t, long M, float smooth, float wb
 int pcms_loss_bwd(const float* x, const float* t, long M, const double* sums, float smooth, float wb,
                   float wd, const float* gout, float* dx, hipStream_t s);
 
+/* ---- Tversky / focal-Tversky region term + focal voxel term (csrc/losses.hip; not in the
+ * reference, whose two losses above stay as they are) ------------------------------------
+ * x (logits), t (targets): NCDHW fp32, groups * nvox elements.  A group is a contiguous run of
+ * nvox elements: groups = 1, nvox = M for region sums over the batch; groups = N*C, nvox =
+ * D*H*W for sums per sample and channel.  Per group, p = sigmoid(x):
+ *   I = sum p t, P = sum p, T = sum t, D = (1-alpha-beta) I + alpha P + beta T + smooth,
+ *   TI = (I + smooth) / D, region_g = max(1 - TI, 0)^gamma          (0 where D <= 0)
+ * per voxel, ce = BCE-with-logits, p_t = p t + (1-p)(1-t):
+ *   v_i = a_i (1 - p_t)^focal_gamma ce, a_i = focal_alpha t + (1-focal_alpha)(1-t), or 1 with
+ *   use_focal_alpha == 0; focal_gamma == 0: v_i = a_i ce
+ *   loss = w_region mean_g region_g + w_voxel (1/M) sum_i v_i
+ * Forward, two launches: per-block fp32 rows [4] = (sum p t, sum p, sum t, sum v) into part
+ * (groups * pcms_region_loss_rows(nvox, groups) * 4 floats; the row count follows
+ * pcms_stream_grid_cap), then one block that sums each group's rows in fp64 in row order into
+ * sums (groups * 4 doubles) and writes loss (one float) and coef (groups * 2 floats): the
+ * backward's (cI, cP) per group, computed in fp64 and rounded once, the 1/groups mean and
+ * w_region folded in, 0 where 1 - TI <= 0.
+ * Backward, one launch: dx_i = gout [ (cI t_i + cP) p (1-p) + (w_voxel / M) a_i dv_i ], gout a
+ * device float or NULL (1).  16-byte accesses on the groups whose base is 16-byte aligned,
+ * scalar ones on the others.  Fixed-order sums: the same bits on every run.  No allocation, no
+ * host synchronisation.  |x| of any size gives finite values; (1 - p_t) == 0 contributes 0.
+ * Negative, no launch: a NULL or misaligned pointer, groups < 1 or > 65535, nvox < 1, groups *
+ * nvox >= 2^31, alpha or beta or smooth < 0, gamma <= 0, focal_gamma neither 0 nor >= 1,
+ * focal_alpha outside [0, 1] with use_focal_alpha, a non-finite parameter.
+ * w_voxel == 0 evaluates no voxel term; focal_gamma == 0 and gamma == 1 evaluate no power.   */
+int pcms_region_loss_rows(long nvox, int groups);
+int pcms_region_loss_fwd(const float* x, const float* t, long nvox, int groups, float alpha, float beta, float gamma,
+                         float smooth, float focal_gamma, int use_focal_alpha, float focal_alpha, float w_region,
+                         float w_voxel, float* part, double* sums, float* coef, float* loss, hipStream_t s);
+int pcms_region_loss_bwd(const float* x, const float* t, long nvox, int groups, float focal_gamma,
+                         int use_focal_alpha, float focal_alpha, float w_voxel, const float* coef, const float* gout,
+                         float* dx, hipStream_t s);
+
 /* ---- torch.optim.Adam(lr, weight_decay=1e-5): utils/trainer.py:113-117 ------------- */
 /* g_eff = s * g + wd * p, s = gscale * (*gmul if gmul != NULL): gscale = 1/world (the
  * data-parallel mean of summed gradients), *gmul = a device-side multiplier (gradient-clip

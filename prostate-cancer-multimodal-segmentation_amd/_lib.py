@@ -105,6 +105,12 @@ SIGNATURES = {
     "pcms_loss_rows": "l",
     "pcms_loss_fwd": "pplfffppps",
     "pcms_loss_bwd": "pplpfffpps",
+    "pcms_region_loss_rows": "li",
+    # x, t, nvox, groups, alpha, beta, gamma, smooth, focal_gamma, use_focal_alpha, focal_alpha,
+    # w_region, w_voxel; part, sums (fp64), coef, loss
+    "pcms_region_loss_fwd": "ppli" + "fffff" + "i" + "fff" + "pppp" + "s",
+    # x, t, nvox, groups, focal_gamma, use_focal_alpha, focal_alpha, w_voxel; coef, gout, dx
+    "pcms_region_loss_bwd": "ppli" + "f" + "i" + "ff" + "ppp" + "s",
     "pcms_adam": "pppplfffffffps",
     "pcms_adam_pack_conv3": "pppppiifffffffps",
     "pcms_adam_pack_convt": "pppppiifffffffps",

@@ -1,5 +1,5 @@
 // What the ops translation units share (ops_layout.hip, ops_bn.hip, ops_pool.hip, ops_head.hip,
-// ops_update.hip): the block size, the capped grid of every grid-stride launch, the storage /
+// ops_update.hip, losses.hip): the block size, the capped grid of every grid-stride launch, the storage /
 // cache-policy dispatch of their launch sites, the BatchNorm-backward element and the two host
 // launchers of kernels that a second family uses.
 #pragma once

@@ -19,7 +19,8 @@ into Adam.
 BatchNorm statistics and the global Dice stay per replica (plain BatchNorm3d).
 
 Config keys follow utils/trainer.py:40-49 (``device``, ``learning_rate``, ``batch_size``,
-``num_epochs``, ``save_dir``, ``validation`` ...) plus ``loss`` ('dice' | 'bce_dice'),
+``num_epochs``, ``save_dir``, ``validation`` ...) plus ``loss`` ('dice' | 'bce_dice' | 'tversky' |
+'focal_tversky' | 'focal' | 'focal_tversky_focal' with ``loss_args``, or a module instance),
 ``precision`` ('bf16' | 'fp32'), ``checkpoint_decoder``, ``device_resample`` (the ``data_dir``
 loaders hand over the files' undecoded volumes and ``data.assemble_batch`` resamples them on
 the GPU, on the copy stream beside the previous step; same batches bit for bit), ``augment`` /
@@ -58,7 +59,7 @@ from ..data import assemble_batch, device_batch, is_raw_batch
 from ..dp import GradSync
 from ..models.unet3d import UNet3D
 from ..optim import FlatAdam
-from .losses import BCEDiceLoss, DiceLoss
+from .losses import BCEDiceLoss, DiceLoss, create_criterion  # noqa: F401  (the loss classes: import parity)
 
 
 class BaseTrainer:
@@ -99,7 +100,13 @@ class BaseTrainer:
                       checkpoint_decoder=self.config.get("checkpoint_decoder", False)).to(self.device)
 
     def _create_criterion(self):
-        return BCEDiceLoss() if self.config.get("loss", "dice") == "bce_dice" else DiceLoss()
+        """``config["loss"]``: a name of ``losses.LOSSES`` ('dice' when the key is missing),
+        constructed with ``config["loss_args"]`` (a dict), or an ``nn.Module`` instance, used as it
+        is; an unknown name raises ValueError.  Under data parallelism the loss stays per replica
+        (as the global Dice does): each rank's region sums run over its own shard.  With a
+        ``per_sample=True`` loss and equal shards the mean over ranks equals the single-process
+        loss, since both terms are then means of per-sample values."""
+        return create_criterion(self.config.get("loss", "dice"), self.config.get("loss_args"))
 
     def _create_optimizer(self):
         return FlatAdam(self.model, lr=self.config["learning_rate"], weight_decay=1e-5)
