@@ -775,6 +775,72 @@ int pcms_joint_histogram(const void* fix, int fdatatype, int Df, int Hf, int Wf,
                          double minter, const float* mlohi, const double* affine12, int sd, int sh, int sw, int bins,
                          unsigned* hist, void* work, hipStream_t s);
 
+/* ---- mutually exclusive classes (csrc/classes.hip; classes.py has the host forms) ----------- */
+/* SoftmaxDiceCELoss.  x: (N, C, nvox) fp32 logits, 2 <= C <= 8; target: the (N, nvox) class map,
+ * fp32 (target_u8 == 0) or uint8, read as it is.  A voxel whose label is not an integer in [0, C)
+ * is ignored: it enters no sum and its gradient is 0.  Per voxel p = softmax_c(x) (the maximum
+ * subtracted, the sum in class order), y the one-hot label.  A group is the batch (per_sample ==
+ * 0) or one sample; over its valid voxels
+ *   I_c = sum p_c y_c, P_c = sum p_c, T_c = sum y_c, dice_c = (2 I_c + smooth) / (P_c + T_c + smooth)
+ *   (1 where the denominator is not positive), region_g = mean_{c in K} (1 - dice_c), K = {1..C-1}
+ *   or {0..C-1} with include_background;
+ *   CE = sum_i w[y_i] (-log p_{y_i}) / sum_i w[y_i] over the batch's valid voxels, 0 without one;
+ *   loss = ce_weight CE + dice_weight mean_g region_g.
+ * class_weights: C HOST floats >= 0 read during the call, or NULL (ones).
+ * Forward, two launches: per-block fp32 rows [3C + 2] = (I_c, P_c, T_c, CE numerator, sum w) into
+ * part (N * pcms_softmax_loss_rows(nvox, N) * (3C + 2) floats, sample-major; the row count follows
+ * pcms_stream_grid_cap), then one block that sums each group's rows in fp64 in a fixed order into
+ * sums (groups * (3C + 2) doubles, groups = N or 1) and writes loss (one float) and coef (groups *
+ * 2C + 1 floats): per group A_c then B_c with dL/dp_c = A_c y_c + B_c (fp64, rounded once,
+ * dice_weight and both means folded in, 0 outside K), then one float ce_weight / sum w (0 without
+ * a valid voxel).
+ * Backward, one launch: dx_k = gout [ p_k (g_k - sum_j p_j g_j) + (ce_weight / sum w) w[y]
+ * (p_k - y_k) ], g_c = A_c y_c + B_c; gout a device float or NULL (1).  Each thread reads its
+ * voxels' C logits from the C planes, four voxels per 16-byte access where nvox % 4 == 0 and the
+ * sample's bases allow it, scalar accesses otherwise.  Fixed-order sums: the same bits on every
+ * run.  Finite results for finite logits of any size.  No allocation, no host synchronisation.
+ * Negative, no launch: a NULL or misaligned pointer, C outside 2..8, N < 1 or > 65535, nvox < 1 or
+ * >= 2^31, smooth < 0, a negative class weight, a non-finite parameter.                        */
+int pcms_softmax_loss_rows(long nvox, int N);
+int pcms_softmax_loss_fwd(const float* x, const void* target, int target_u8, long nvox, int N, int C, int per_sample,
+                          int include_background, float smooth, float ce_weight, float dice_weight,
+                          const float* class_weights, float* part, double* sums, float* coef, float* loss,
+                          hipStream_t s);
+int pcms_softmax_loss_bwd(const float* x, const void* target, int target_u8, long nvox, int N, int C, int per_sample,
+                          const float* class_weights, const float* coef, const float* gout, float* dx,
+                          hipStream_t s);
+/* Class-map labels: pcms_resample_label's / pcms_resample_affine_label's nearest index rules and
+ * decoding, bit for bit, with a table in place of `> 0`: out = j + 1 (fp32) for the first j with
+ * fl32(decoded value) == class_values[j], else 0 (also outside the source).  class_values:
+ * n_values (1..7) finite HOST floats copied into the kernel arguments.  Equal to
+ * classes.classes_of(resample.resample(vol, target, nearest=True), class_values) and to the same
+ * after resample.resample_affine(..., nearest=True), byte for byte.  Negative, no launch: the
+ * label entry points' cases, a NULL table, n_values outside 1..7, a non-finite value.          */
+int pcms_resample_classes(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope, double scl_inter,
+                          const float* class_values, int n_values, float* out, int D, int H, int W, hipStream_t s);
+int pcms_resample_affine_classes(const void* src, int datatype, int Di, int Hi, int Wi, double scl_slope,
+                                 double scl_inter, const double* affine12, const float* class_values, int n_values,
+                                 float* out, int D, int H, int W, hipStream_t s);
+/* logits (B, C, n) fp32 -> probs (C, B, n), class-major, so that the B volumes of a class are
+ * contiguous (pcms_flip_mean takes them as they are): m = max_c x_c, e_c = expf(x_c - m), s summed
+ * in class order, p_c = e_c / s.  16-byte accesses where n % 4 == 0 and both bases allow it.
+ * Negative, no launch: a NULL or misaligned pointer, overlapping buffers, B or n < 1, C outside
+ * 2..8.                                                                                        */
+int pcms_softmax_planes(const float* logits, int B, int C, long n, float* probs, hipStream_t s);
+/* classes.labels_on_grid: probs (C, Dt, Ht, Wt) -> labels (D, H, W) uint8.  pcms_prob_to_mask's
+ * linear gather runs on every class plane (the same bits); the label is the class of the largest
+ * value, the first one winning (strict >), so a voxel outside the volume (all zeros) gets class
+ * 0.  probs_native (C, D, H, W fp32) receives the gathered planes unless NULL.  Negative, no
+ * launch: a NULL or misaligned pointer, C outside 1..8, an extent below 1.                     */
+int pcms_probs_to_labels(const float* probs, int C, int Dt, int Ht, int Wt, unsigned char* labels, float* probs_native,
+                         int D, int H, int W, hipStream_t s);
+/* counts[3 c + (0, 1, 2)] = |pred == c|, |ref == c|, |pred == c and ref == c| for c < C over two
+ * uint8 class maps of n voxels (counts: 3 C DEVICE int64, zeroed on s by the call).  Integer
+ * atomics aggregated over the lanes of a wave that share a class: exact, the same on every run.
+ * Negative, no launch: a NULL pointer, misaligned counts, n < 1, C outside 1..8.               */
+int pcms_class_overlap(const unsigned char* pred, const unsigned char* ref, long n, int C, long* counts,
+                       hipStream_t s);
+
 /* ---- measurement (bench.py, not a training path) ----------------------------------- */
 /* One launch of nblocks single-wave workgroups; block b writes {s_memtime, s_memrealtime,
  * XCC id} to out[3b .. 3b+2] (uint64).  Two probes around a stretch of work give each XCD's

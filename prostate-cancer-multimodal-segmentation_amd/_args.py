@@ -29,7 +29,7 @@ def device_tensor(t, dtype: torch.dtype, ndim: int, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
-# The two arrays below are kernel *arguments* in host memory: the entry point reads them during the
+# The arrays below are kernel *arguments* in host memory: the entry point reads them during the
 # call (``ctypes.addressof``), so the caller keeps the returned object in a local until ``call``
 # returns -- a temporary would be freed before the C side looks at it.
 def host_affine12(twelve):
@@ -40,6 +40,11 @@ def host_affine12(twelve):
 def host_ints(values):
     """Flip masks (or any ints) as the ``int`` array an entry point reads during the call."""
     return (ctypes.c_int * len(values))(*values)
+
+
+def host_floats(values):
+    """Class weights or class values as the ``float`` array an entry point reads during the call."""
+    return (ctypes.c_float * len(values))(*(float(v) for v in values))
 
 
 def volume3(mask) -> np.ndarray:

@@ -158,6 +158,17 @@ SIGNATURES = {
     # fixed then moving volume (src, datatype, D, H, W, slope, inter, lohi: device), affine12: host;
     # sd, sh, sw, bins; hist, work: device pointers
     "pcms_joint_histogram": "piiiiddp" + "piiiiddp" + "p" + "iiii" + "pp" + "s",
+    "pcms_softmax_loss_rows": "li",
+    # x, target, target_u8, nvox, N, C, per_sample, include_background, smooth, ce_weight, dice_weight,
+    # class_weights (host or None); part, sums (fp64), coef, loss
+    "pcms_softmax_loss_fwd": "ppi" + "liiii" + "fff" + "p" + "pppp" + "s",
+    # x, target, target_u8, nvox, N, C, per_sample, class_weights (host or None); coef, gout, dx
+    "pcms_softmax_loss_bwd": "ppi" + "liii" + "p" + "ppp" + "s",
+    "pcms_resample_classes": "piiiidd" + "pi" + "piiis",  # class_values: a host pointer (ctypes.addressof)
+    "pcms_resample_affine_classes": "piiiidd" + "p" + "pi" + "piiis",  # affine12, class_values: host pointers
+    "pcms_softmax_planes": "piilps",
+    "pcms_probs_to_labels": "piiii" + "pp" + "iiis",
+    "pcms_class_overlap": "pplips",
     "pcms_clock_probe": "pis",
     "pcms_clock_spin": "pils",
 }

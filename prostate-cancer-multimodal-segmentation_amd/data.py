@@ -39,6 +39,10 @@ a case on the reference file's grid through the files' world geometry instead of
 onto the grid: ``world_matrix`` / ``align_affine`` / ``compose_affine`` / ``case_affine`` on the
 host, the same twelve doubles per volume in the existing affine launches on the device, with the
 rigid ``corrections`` of ``align.register_dataset`` when given; the same batches bit for bit.
+``n_classes=C`` (with ``class_values``; dataset, loader, ``assemble_batch``, ``Trainer`` config;
+DESIGN §0t) keeps the label a class map instead of binarising it: ``classes.classes_of`` of the
+nearest-resampled label on the host, pcms_resample_classes / pcms_resample_affine_classes on the
+device, the same batches byte for byte; ``n_classes=1`` is everything above, untouched.
 The reference's SimpleITK ``SetSize`` takes (x, y, z), so its non-cubic outputs come out
 axis-reversed; here ``target_size`` is (D, H, W) as documented (:41).
 """
@@ -57,6 +61,7 @@ from torch.utils.data import DataLoader, Dataset
 from ._args import axes3, host_affine12, host_ints
 from ._lib import call, query
 from .align import Alignment
+from .classes import check_n_classes, class_values_of, classes_of
 from .geometry import (RIGID_NAMES, affine12_of, align_affine, case_affine, compose_affine,  # noqa: F401
                        compose_transform, registration_fixed, rigid_correction, rigid_world, volume_affine,
                        world_centre, world_matrix)
@@ -346,14 +351,17 @@ def is_raw_batch(batch) -> bool:
     return isinstance(batch, dict) and "raw_images" in batch
 
 
-def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] = None, device=None) -> Dict:
+def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] = None, device=None,
+                   class_values=None) -> Dict:
     """A ``device_resample`` loader's batch -> ``{'image': (N, M, D, H, W) f32, 'label':
     (N, 1, D, H, W) f32, 'case_id': [...]}`` on ``device``, equal to the default loader's
     batch: each volume's bytes go up from pinned memory in their native type and one resample
     launch writes its channel plane; ``None`` channels (zero_fill) are zeroed.  Everything is
-    enqueued on the current stream.  ``target_size`` defaults to the one the loader recorded."""
+    enqueued on the current stream.  ``target_size`` defaults to the one the loader recorded.
+    A batch of a ``n_classes > 1`` loader carries its ``class_values`` (``class_values=`` here
+    overrides them): the label plane then holds class indices (``resample_device``'s ``class_values``)."""
     if "patches" in raw_batch:  # a patch-training loader's batch: the grid and the patch shape ride along
-        return assemble_patch_batch(raw_batch, device)
+        return assemble_patch_batch(raw_batch, device, class_values)
     target = tuple(int(v) for v in (target_size if target_size is not None else raw_batch["target_size"]))
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
@@ -362,6 +370,8 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
     images, labels = raw_batch["raw_images"], raw_batch["raw_label"]
     n, m = len(images), len(images[0])
     aug = raw_batch.get("augment")  # per case: the drawn (affines, label affine, gains, biases[, field]), or absent
+    # a class-map loader's table, or absent: the binary label
+    values = class_values if class_values is not None else raw_batch.get("class_values")
     with torch.cuda.device(device):
         image = torch.empty((n, m) + target, dtype=torch.float32, device=device)
         label = torch.empty((n, 1) + target, dtype=torch.float32, device=device)
@@ -381,12 +391,13 @@ def assemble_batch(raw_batch: Dict, target_size: Optional[Tuple[int, int, int]] 
                 else:
                     resample_device(up(raw), target, out=image[i, c], affine=aug[i]["affine"][c],
                                     gain=aug[i]["gain"][c], bias=aug[i]["bias"][c], field=field)
+            # (an elastic field never comes with a class table: the dataset refuses the pair)
             resample_device(up(labels[i]), target, nearest=True, out=label[i, 0],
-                            affine=None if aug is None else aug[i]["label_affine"], field=field)
+                            affine=None if aug is None else aug[i]["label_affine"], field=field, class_values=values)
     return {"image": image, "label": label, "case_id": list(raw_batch["case_id"])}
 
 
-def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
+def assemble_patch_batch(raw_batch: Dict, device=None, class_values=None) -> Dict:
     """A patch-training ``device_resample`` batch -> ``{'image': (N*P, M, wd, wh, ww) f32,
     'label': (N*P, 1, wd, wh, ww) f32, 'case_id': [...], 'picks': (N, 3P + 1) int32}`` on
     ``device``, equal to the host loader's batch bit for bit.  Per case: the bytes go up once; one
@@ -397,7 +408,9 @@ def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
     ``normalise``, or after pcms_volume_window and through pcms_patch_resample_window when the
     batch's ``"normalise"`` entry selects the percentile window; ``None`` channels are zeroed),
     and one pcms_window_gather cuts the label patches.  Everything is enqueued on the current
-    stream, with no host synchronisation."""
+    stream, with no host synchronisation.  With the ``class_values`` of a ``n_classes > 1`` loader
+    the grid label is a class map (pcms_resample_affine_classes); the origins are still picked on
+    ``label > 0``, any foreground class."""
     device = torch.device(device if device is not None else "cuda")
     if device.type != "cuda":
         raise RuntimeError(f"a device_resample batch can only be assembled on a GPU, not on '{device}': "
@@ -406,6 +419,7 @@ def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
     patch = tuple(int(v) for v in raw_batch["patch_size"])
     norm = Normalisation.of(raw_batch["normalise"])
     normalise = norm is not None
+    values = class_values if class_values is not None else raw_batch.get("class_values")
     n, m = len(images), len(images[0])
     P = int(draws[0]["rank_u"].numel())
     nwin = patch[0] * patch[1] * patch[2]
@@ -426,7 +440,7 @@ def assemble_patch_batch(raw_batch: Dict, device=None) -> Dict:
             if int(d["rank_u"].numel()) != P:
                 raise ValueError("every case of a batch holds the same number of patches")
             lab = labels[i] if labels[i].data.device.type == "cuda" else labels[i].pin_memory().to(device, True)
-            label_grid = resample_device(lab, grid, nearest=True, affine=d["label_affine"])
+            label_grid = resample_device(lab, grid, nearest=True, affine=d["label_affine"], class_values=values)
             work = torch.empty(query("pcms_foreground_pick_work_ints", cells), dtype=torch.int32, device=device)
             call("pcms_foreground_pick", label_grid, cells, *grid, *patch, up(d["rank_u"]), up(d["fallback"]), P,
                  picks[i], work)
@@ -459,13 +473,16 @@ class _CollateRaw:
     """Collate of ``device_resample`` samples: raw shapes differ between cases and modalities,
     so the descriptors stay in lists (nothing is stacked); the target size rides along."""
 
-    def __init__(self, target_size, patches=None):
+    def __init__(self, target_size, patches=None, class_values=None):
         self.target_size = tuple(int(v) for v in target_size)
         self.patches = PatchSampling.of(patches)
+        self.class_values = class_values  # a class-map dataset's table (None: binary labels)
 
     def __call__(self, samples: List[Dict]) -> Dict:
         batch = {"raw_images": [s["raw_images"] for s in samples], "raw_label": [s["raw_label"] for s in samples],
                  "case_id": [s["case_id"] for s in samples], "target_size": self.target_size}
+        if self.class_values is not None:
+            batch["class_values"] = self.class_values
         if samples and "augment" in samples[0]:  # an augmenting dataset: each case's drawn transform rides along
             batch["augment"] = [s["augment"] for s in samples]
         if self.patches is not None:  # a patch-training dataset: each case's affines and patch draws (CPU tensors)
@@ -498,7 +515,7 @@ class ProstateDataset(Dataset):
     def __init__(self, data_dir: str, modalities: Optional[List[str]] = None, missing_strategy: str = "zero_fill",
                  target_size: Tuple[int, int, int] = (128, 128, 128), is_training: bool = True,
                  data_type: str = "BPH", device_resample: bool = False, augment=None, augment_seed: int = 0,
-                 patches=None, align=None, corrections=None):
+                 patches=None, align=None, corrections=None, n_classes: int = 1, class_values=None):
         """``augment`` (an ``Augment`` or a dict of its fields; None: off, every sample as
         before): each case is resampled under a transform drawn by ``draw_transform(augment,
         augment_seed, epoch, case index)``, one geometry for all its modalities and its label,
@@ -519,7 +536,17 @@ class ProstateDataset(Dataset):
         give the same batches.  ``corrections`` (``align.register_dataset``'s dict ``{case_id:
         {modality: six parameters}}`` or the path of its JSON; needs ``align``): the rigid
         correction of each modality goes into its map.  Training never registers on the fly:
-        ``mode="register"`` without ``corrections`` raises."""
+        ``mode="register"`` without ``corrections`` raises.
+        ``n_classes`` (default 1: the binary label ``> 0``, every sample as before) with
+        ``class_values`` (default ``(1, .., n_classes - 1)``): the label stays a class map --
+        ``classes.classes_of`` of the nearest-resampled label file, class ``j + 1`` where its value
+        is ``class_values[j]`` and 0 elsewhere -- as fp32 ``(1, D, H, W)``.  Patches are still
+        picked on ``label > 0``, any foreground class.  Elastic deformation of a class map is not
+        supported (ValueError)."""
+        self.n_classes = check_n_classes(n_classes)
+        if class_values is not None and self.n_classes == 1:
+            raise ValueError("class_values need n_classes > 1")
+        self.class_values = class_values_of(self.n_classes, class_values) if self.n_classes > 1 else None
         if missing_strategy not in ("zero_fill", "skip", "duplicate"):
             raise ValueError(f"unsupported missing-modality strategy: {missing_strategy}")
         self.augment = Augment.of(augment)
@@ -527,6 +554,9 @@ class ProstateDataset(Dataset):
         if self.patches is not None and self.augment is not None and self.augment.elastic:
             raise ValueError("patches and Augment.elastic_grid cannot be combined: the patch resampler has no "
                              "deforming form")
+        if self.class_values is not None and self.augment is not None and self.augment.elastic:
+            raise ValueError("Augment.elastic_grid and n_classes > 1 cannot be combined: the deforming resampler has "
+                             "no class-map form")
         self.align = Alignment.of(align)
         if isinstance(corrections, (str, os.PathLike)):
             import json
@@ -627,6 +657,12 @@ class ProstateDataset(Dataset):
             out[m] = (ref_shape, align_affine(ref_geo, read_nifti_geometry(p), T))
         return out
 
+    def _label_of(self, nearest: np.ndarray) -> np.ndarray:
+        """The (D, H, W) fp32 label of a nearest-resampled label volume: ``> 0``, or the class map."""
+        if self.class_values is None:
+            return (nearest > 0).astype(np.float32)
+        return classes_of(nearest, self.class_values)
+
     def set_epoch(self, epoch: int) -> None:
         """The epoch whose transforms and patch origins ``__getitem__`` draws (no effect without
         ``augment`` or ``patches``).
@@ -671,7 +707,7 @@ class ProstateDataset(Dataset):
             vol = self._first_volume(read_nifti(p)).astype(np.float32)
             chans.append(sample(vol, al and al[m], gain=tf.gain[c], bias=tf.bias[c]))
         lab = self._first_volume(read_nifti(case["label_path"]))
-        label = (sample(lab, al and al["label"], nearest=True) > 0).astype(np.float32)[None]
+        label = self._label_of(sample(lab, al and al["label"], nearest=True))[None]
         return {"image": torch.from_numpy(np.stack(chans, 0)).float(), "label": torch.from_numpy(label),
                 "case_id": case["case_id"]}
 
@@ -705,8 +741,8 @@ class ProstateDataset(Dataset):
         lab = self._first_volume(read_nifti(case["label_path"]))
         grid = ps.grid if ps.grid is not None else tuple(lab.shape) if al is None else al["label"][0]
         rank_u, fallback = draw_patches(ps, ps.seed, self.epoch, idx, grid)
-        label_grid = (resample_affine(lab, grid, *tf.affine(lab.shape, grid, al and al["label"]), nearest=True)
-                      > 0).astype(np.float32)
+        label_grid = self._label_of(resample_affine(lab, grid, *tf.affine(lab.shape, grid, al and al["label"]),
+                                                    nearest=True))
         origins, count = pick_origins(label_grid, ps.patch_size, rank_u, fallback)
         P = ps.patches_per_case
         image = np.zeros((P, len(self.modalities)) + ps.patch_size, dtype=np.float32)
@@ -747,6 +783,10 @@ class ProstateDataset(Dataset):
                 vol = resample(vol, self.target_size)
             chans.append(vol)
         lab = self._first_volume(read_nifti(case["label_path"]))
+        if self.class_values is not None:  # (always through resample: its fp32 values are what the table names)
+            label = classes_of(resample(lab, self.target_size, nearest=True), self.class_values)[None]
+            return {"image": torch.from_numpy(np.stack(chans, 0)).float(), "label": torch.from_numpy(label),
+                    "case_id": case["case_id"]}
         if lab.shape != self.target_size:
             lab = resample(lab, self.target_size, nearest=True)
         label = (lab > 0).astype(np.float32)[None]
@@ -758,7 +798,8 @@ def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, mod
                    missing_strategy: str = "zero_fill", target_size=(128, 128, 128), num_workers: int = 0,
                    is_training: bool = True, data_type: str = "BPH", indices=None, rank: int = 0,
                    world_size: int = 1, device_resample: bool = False, augment=None,
-                   augment_seed: int = 0, patches=None, align=None, corrections=None) -> DataLoader:
+                   augment_seed: int = 0, patches=None, align=None, corrections=None, n_classes: int = 1,
+                   class_values=None) -> DataLoader:
     """script/data_loader.py:421-466 (pinned host batches; Trainer stages them to the GPU on
     a copy stream one batch ahead).  ``world_size > 1``: each rank iterates its own
     DistributedSampler shard (call ``loader.sampler.set_epoch(epoch)`` every epoch).
@@ -773,13 +814,16 @@ def get_dataloader(data_dir: str, batch_size: int = 2, shuffle: bool = True, mod
     the origins and the foreground count per case; ``target_size`` is unused.  Both kinds of
     loader give equal batches here too (``assemble_patch_batch``).
     ``align`` / ``corrections``: the volumes are placed by their world geometry
-    (``ProstateDataset``); both kinds of loader give equal batches with it as well."""
+    (``ProstateDataset``); both kinds of loader give equal batches with it as well.
+    ``n_classes`` / ``class_values``: class-map labels (``ProstateDataset``); both kinds of loader
+    give equal batches with them too."""
     patches = PatchSampling.of(patches)
     ds = ProstateDataset(data_dir, modalities=modalities, missing_strategy=missing_strategy,
                          target_size=target_size, is_training=is_training, data_type=data_type,
                          device_resample=device_resample, augment=augment, augment_seed=augment_seed,
-                         patches=patches, align=align, corrections=corrections)
-    collate = _CollateRaw(target_size, patches) if device_resample else None
+                         patches=patches, align=align, corrections=corrections, n_classes=n_classes,
+                         class_values=class_values)
+    collate = _CollateRaw(target_size, patches, ds.class_values) if device_resample else None
     if patches is not None and not device_resample:
         collate = _collate_patches
     if indices is not None:

@@ -26,7 +26,9 @@ public name of those modules is also a name of this one:
 * ``window`` (§0o): sliding windows, their blend, ``tta_mean``;
 * ``components`` (§0k): connected components and mask post-processing;
 * ``lesions`` (§0n): per-lesion tables and detection scores;
-* ``distance`` (§0l): surfaces, the exact distance transform, HD / HD95 / ASSD.
+* ``distance`` (§0l): surfaces, the exact distance transform, HD / HD95 / ASSD;
+* ``classes`` (§0t): softmax planes, the class map on the native grid, per-class overlap --
+  ``ModelPredictor(..., n_classes=C)`` predicts mutually exclusive classes with them.
 """
 from __future__ import annotations
 
@@ -44,6 +46,8 @@ from .align import (DEFAULT_LEVELS, MODALITIES, Alignment, _aligned_affines, _ca
                     _case_reference, _fixed_modality, joint_histogram, joint_histogram_device,
                     normalised_mutual_information, register_case, register_case_device, register_dataset,
                     register_rigid, register_rigid_device)
+from .classes import (check_n_classes, class_overlap_device, class_values_of, classes_of,  # noqa: F401
+                      labels_on_grid, labels_on_grid_device, scores_of_counts, softmax_planes_device)
 from .components import (MAX_KEEP_LARGEST, _check_filter, _check_status, _offsets,  # noqa: F401
                          _postprocess_enqueue, fill_holes, filter_components, label_components,
                          label_components_device, postprocess, postprocess_device)
@@ -254,7 +258,8 @@ class CasePrediction:
     ``predict_case`` was asked for it; ``alignment``: with ``align``, per present modality
     ``{"params": (tz, ty, tx, rz, ry, rx), "before": .., "after": ..}`` -- the rigid correction
     and the similarity before and after it (zeros and None where nothing was registered) -- else
-    None."""
+    None.  From a predictor of ``n_classes > 1`` the ``mask`` holds class indices, the
+    ``probability`` is (C, z, y, x) and every row of ``lesions`` carries its ``"class"``."""
     mask: np.ndarray
     probability: Optional[np.ndarray]
     reference_path: str
@@ -268,9 +273,15 @@ def preprocess_image(image: np.ndarray) -> torch.Tensor:
 
 
 class ModelPredictor:
-    def __init__(self, model_path: str, device: str = "cuda", precision: str = "bf16"):
+    def __init__(self, model_path: str, device: str = "cuda", precision: str = "bf16", n_classes: int = 1,
+                 class_values=None):
+        """``n_classes > 1``: the network emits that many logit planes and ``predict_case``
+        returns a class map; ``class_values`` (default ``(1, .., n_classes - 1)``) are
+        the values a label file gives the foreground classes, for ``score_case``."""
         self.device = torch.device(device)
-        self.model = UNet3D(n_modalities=5, n_classes=1, precision=precision).to(self.device)
+        self.n_classes = check_n_classes(n_classes)
+        self.class_values = class_values_of(n_classes, class_values) if n_classes > 1 else None
+        self.model = UNet3D(n_modalities=5, n_classes=n_classes, precision=precision).to(self.device)
         load_weights(self.model, model_path)
         self.model.eval()
 
@@ -332,7 +343,22 @@ class ModelPredictor:
         rigid registration on the device (``"register"``) instead of being stretched onto it.  The
         reference defaults to ``output_like``, else the first present modality's file;
         ``target_size=None`` is its native grid and the modalities' shapes may differ.  The
-        result's ``alignment`` reports the corrections.  ``align=None``: nothing changes."""
+        result's ``alignment`` reports the corrections.  ``align=None``: nothing changes.
+        A predictor of ``n_classes > 1``: the logits of the batch go through
+        pcms_softmax_planes (class-major), each class's flipped copies through pcms_flip_mean, and
+        pcms_probs_to_labels (``classes.labels_on_grid``) gives the class map on the native grid --
+        the class of the largest probability, the first one on a tie; ``threshold`` is unused.
+        ``keep_largest`` / ``min_voxels`` / ``fill_holes`` run pcms_mask_postprocess once per
+        foreground class on ``labels == c``: a removed voxel becomes 0, a filled hole takes the
+        class where it was background.  ``return_lesions`` tables every class's components with
+        that class's probability plane.  ``window`` raises ValueError there."""
+        if self.n_classes > 1:
+            if window is not None:
+                raise ValueError("sliding-window prediction of n_classes > 1 is not supported: the blend takes one "
+                                 "probability plane")
+            return self._predict_case_classes(case_dir, target_size, handle_missing, normalise, tta_flips, output_like,
+                                              return_probability, keep_largest, min_voxels, fill_holes, connectivity,
+                                              return_lesions, align)
         align = Alignment.of(align)
         if align is not None and align.to is None and output_like is not None:
             align = dataclasses.replace(align, to=output_like)
@@ -383,6 +409,82 @@ class ModelPredictor:
         return CasePrediction(mask_host, prob_native.cpu().numpy() if return_probability else None, reference,
                               geometry, lesions, alignment)
 
+    def _predict_case_classes(self, case_dir, target_size, handle_missing, normalise, tta_flips, output_like,
+                              return_probability, keep_largest, min_voxels, fill_holes, connectivity, return_lesions,
+                              align) -> CasePrediction:
+        """``predict_case`` of a predictor of ``n_classes > 1`` (its docstring has the steps)."""
+        align = Alignment.of(align)
+        if align is not None and align.to is None and output_like is not None:
+            align = dataclasses.replace(align, to=output_like)
+        masks = _flip_masks(tta_flips)
+        _check_filter(keep_largest, min_voxels)
+        _offsets(connectivity)
+        post = keep_largest != 0 or min_voxels > 1 or bool(fill_holes)
+        x, alignment = prepare_case_device(case_dir, target_size, handle_missing, normalise, self.device, align,
+                                           return_alignment=True)  # raises if none present
+        reference = output_like if output_like is not None else \
+            next(p for p in _case_files(case_dir) if p is not None) if align is None else \
+            _case_reference(_case_files(case_dir), align)
+        native = tuple(int(v) for v in read_nifti_header(reference)["shape_xyz"][:3][::-1])
+        geometry = read_nifti_geometry(reference)
+        grid = tuple(x.shape[2:])
+        C = self.n_classes
+        self.model.eval()
+        with torch.no_grad(), torch.cuda.device(self.device):
+            batch = torch.cat([x] + [torch.flip(x, dims=[2 + a for a in f]) for f in tta_flips], dim=0)
+            probs = softmax_planes_device(self.model(batch))  # (C, k, D, H, W): a class's k volumes are contiguous
+            if len(masks) > 1:
+                host = host_ints(masks)  # read during the calls: stays in this local until the last one returns
+                mean = torch.empty((C,) + grid, dtype=torch.float32, device=self.device)
+                for c in range(C):
+                    call("pcms_flip_mean", probs[c], len(masks), ctypes.addressof(host), mean[c], *grid)
+            else:
+                mean = probs[:, 0]
+            labels, planes = labels_on_grid_device(mean, native, return_probability or return_lesions)
+            if post:
+                for c in range(1, C):
+                    own = (labels == c).to(torch.uint8)
+                    kept, work = _postprocess_enqueue(own, keep_largest, min_voxels, fill_holes, connectivity)
+                    _check_status(int(work[0].item()), "predict_case")
+                    labels = torch.where((own != 0) & (kept == 0), torch.zeros_like(labels), labels)
+                    labels = torch.where((kept != 0) & (labels == 0), torch.full_like(labels, c), labels)
+            lesions = None
+            if return_lesions:
+                spacing = tuple(float(v) for v in geometry["pixdim"][1:4])[::-1]
+                lesions = []
+                for c in range(1, C):
+                    rows = lesion_table_device((labels == c).to(torch.uint8), planes[c], spacing, connectivity)
+                    lesions.extend(dict(r, **{"class": c}) for r in rows)
+            mask_host = labels.cpu().numpy()
+        return CasePrediction(mask_host, planes.cpu().numpy() if return_probability else None, reference, geometry,
+                              lesions, alignment)
+
+    def _score_case_classes(self, result: CasePrediction, label_path: str, lesion_metrics: bool, min_iou: float,
+                            connectivity: int) -> dict:
+        """``score_case`` of a predictor of ``n_classes > 1``."""
+        label = classes_of(_first_volume(read_nifti(label_path)), self.class_values).astype(np.uint8)
+        if tuple(label.shape) != tuple(result.mask.shape):
+            raise ValueError(f"label of shape {tuple(label.shape)} is not on the grid {tuple(result.mask.shape)} of "
+                             "the mask")
+        spacing = tuple(float(v) for v in result.geometry["pixdim"][1:4])[::-1]
+        with torch.cuda.device(self.device):
+            mask = torch.from_numpy(np.ascontiguousarray(result.mask, dtype=np.uint8)).to(self.device)
+            lab = torch.from_numpy(np.ascontiguousarray(label)).to(self.device)
+            dice, iou = scores_of_counts(class_overlap_device(mask, lab, self.n_classes).cpu().numpy())
+            per_class = []
+            for c in range(1, self.n_classes):
+                mc, lc = (mask == c).to(torch.uint8), (lab == c).to(torch.uint8)
+                row = {"class": c, "dice": dice[c], "iou": iou[c]}
+                row.update(surface_metrics_device(mc, lc, spacing))
+                if lesion_metrics:
+                    prob = None if result.probability is None else \
+                        torch.from_numpy(np.ascontiguousarray(result.probability[c], dtype=np.float32)).to(self.device)
+                    row["lesions"] = lesion_metrics_device(mc, lc, prob, spacing, connectivity, min_iou)
+                per_class.append(row)
+        fg = max(self.n_classes - 1, 1)
+        return {"dice": sum(dice[1:]) / fg, "iou": sum(iou[1:]) / fg, "class_dice": dice, "class_iou": iou,
+                "classes": per_class}
+
     def score_case(self, result: CasePrediction, label_path: str, lesion_metrics: bool = False,
                    min_iou: float = 0.1, connectivity: int = 26) -> dict:
         """Score ``result.mask`` against the label file ``label_path`` (binarised with ``!= 0``)
@@ -392,7 +494,15 @@ class ModelPredictor:
         dict gains ``"lesions"``: ``lesion_metrics_device`` of mask against label at
         ``connectivity`` and ``min_iou``, in the same spacing, the predicted lesions' confidence
         from ``result.probability`` when the result carries it.  ValueError if the label is not on
-        the mask's grid."""
+        the mask's grid.
+        A predictor of ``n_classes > 1``: the label becomes a class map through ``class_values``
+        (``classes.classes_of``); ``class_dice`` / ``class_iou`` list every class's score
+        (pcms_class_overlap; a class absent from both maps scores 1.0), ``dice`` / ``iou`` are
+        their means over the foreground classes, and ``classes`` holds per foreground class the
+        scores above, the surface metrics and, when asked, the lesion metrics of ``mask == c``
+        against ``label == c``."""
+        if self.n_classes > 1:
+            return self._score_case_classes(result, label_path, lesion_metrics, min_iou, connectivity)
         label = _first_volume(read_nifti(label_path)) != 0
         if tuple(label.shape) != tuple(result.mask.shape):
             raise ValueError(f"label of shape {tuple(label.shape)} is not on the grid {tuple(result.mask.shape)} of "

@@ -7,7 +7,8 @@ results are parity-unpinned beyond the tests' closed-form cases (identity, integ
 constant and linear ramps).  ``resample_affine`` is the same gather under a full 3x4 affine
 (training-time augmentation, alignment), ``resample_deform`` adds a cubic B-spline displacement in
 front of it.  ``resample_device`` runs all of them on a ``RawVolume`` whose bytes are on the GPU
-(pcms_resample_linear / _label, pcms_resample_affine_*, pcms_resample_deform_*), bit for bit.
+(pcms_resample_linear / _label, pcms_resample_affine_*, pcms_resample_deform_*), bit for bit, and
+with ``class_values`` the class-map labels of csrc/classes.hip.
 """
 from __future__ import annotations
 
@@ -17,7 +18,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from ._args import host_affine12
+from ._args import host_affine12, host_floats
 from ._lib import call
 from .nifti import RawVolume, device_raw
 
@@ -204,7 +205,8 @@ def resample_deform(vol: np.ndarray, target: Tuple[int, int, int], A, t, field, 
 
 def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool = False,
                     out: Optional[torch.Tensor] = None, affine: Optional[Sequence[float]] = None,
-                    gain: float = 1.0, bias: float = 0.0, field: Optional[torch.Tensor] = None) -> torch.Tensor:
+                    gain: float = 1.0, bias: float = 0.0, field: Optional[torch.Tensor] = None,
+                    class_values: Optional[Sequence[float]] = None) -> torch.Tensor:
     """``resample`` of a volume whose bytes are on the GPU, on the current stream: the linear
     form equals ``resample(vol.astype(float32), target)`` bit for bit, ``nearest=True`` gives
     the binarised label ``resample(vol, target, nearest=True) > 0`` as fp32 {0, 1} (for a
@@ -216,9 +218,21 @@ def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool 
     ``nearest``, ``resample_affine(vol, target, A, t, nearest=True) > 0``, bit for bit.
     ``field`` (a contiguous fp64 ``(gd, gh, gw, 3)`` tensor on the volume's device; needs
     ``affine``) selects the deforming entry points: ``resample_deform`` with that control grid
-    in place of ``resample_affine``, bit for bit again."""
+    in place of ``resample_affine``, bit for bit again.
+    ``class_values`` (1..7 label-file values; needs ``nearest``, no ``field``) selects the class-map
+    entry points pcms_resample_classes / pcms_resample_affine_classes: the same nearest gather,
+    then ``classes.classes_of(., class_values)`` in place of ``> 0`` -- class ``j + 1`` where the
+    fp32 value is ``class_values[j]``, else 0 -- byte for byte."""
     target = tuple(int(v) for v in target)
     raw = device_raw(raw, "resample_device")
+    table = None
+    if class_values is not None:
+        if not nearest or field is not None:
+            raise ValueError("class_values select the class-map label: they need nearest=True and no field (an "
+                             "elastic deformation of a class map is not supported)")
+        if not 1 <= len(class_values) <= 7:
+            raise ValueError(f"class_values holds 1..7 values, got {tuple(class_values)!r}")
+        table = host_floats(class_values)  # read during the call: stays in this local until it returns
     if out is None:
         out = torch.empty(target, dtype=torch.float32, device=raw.data.device)
     elif (tuple(out.shape) != target or out.dtype != torch.float32 or not out.is_contiguous()
@@ -227,6 +241,9 @@ def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool 
     if affine is None:
         if field is not None:
             raise ValueError("field needs affine: the deformation is applied in front of the affine")
+        if table is not None:
+            call("pcms_resample_classes", *raw.kernel_args(), ctypes.addressof(table), len(class_values), out, *target)
+            return out
         call("pcms_resample_label" if nearest else "pcms_resample_linear", *raw.kernel_args(), out, *target)
         return out
     if len(affine) != 12:
@@ -243,7 +260,10 @@ def resample_device(raw: RawVolume, target: Tuple[int, int, int], nearest: bool 
             call("pcms_resample_deform_linear", *raw.kernel_args(), ctypes.addressof(host), field, *grid, float(gain),
                  float(bias), out, *target)
         return out
-    if nearest:
+    if table is not None:
+        call("pcms_resample_affine_classes", *raw.kernel_args(), ctypes.addressof(host), ctypes.addressof(table),
+             len(class_values), out, *target)
+    elif nearest:
         call("pcms_resample_affine_label", *raw.kernel_args(), ctypes.addressof(host), out, *target)
     else:
         call("pcms_resample_affine_linear", *raw.kernel_args(), ctypes.addressof(host), float(gain), float(bias), out,

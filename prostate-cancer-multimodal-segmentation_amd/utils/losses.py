@@ -12,6 +12,10 @@ two losses above are untouched): ``TverskyLoss``, ``FocalTverskyLoss``, ``FocalL
 ``FocalTverskyFocalLoss`` and the general ``RegionVoxelLoss`` -- a Tversky / focal-Tversky region
 term over the batch or per (sample, channel) volume plus a focal voxel term; the fp64 definition
 is ``region_voxel_loss_host``.
+
+For mutually exclusive classes (csrc/classes.hip): ``SoftmaxDiceCELoss`` -- softmax cross-entropy
+plus a per-class Dice on ``(N, C, ...)`` logits against a class map; the fp64 definition is
+``classes.softmax_dice_ce_loss_host``.
 """
 from __future__ import annotations
 
@@ -20,6 +24,7 @@ import torch.nn as nn
 
 from .. import _lib
 from .._lib import call, query
+from ..classes import _validate_loss, softmax_dice_ce_loss
 
 
 class _LossFunction(torch.autograd.Function):
@@ -272,9 +277,34 @@ class FocalTverskyFocalLoss(RegionVoxelLoss):
                          per_sample=per_sample)
 
 
+class SoftmaxDiceCELoss(nn.Module):
+    """``ce_weight`` * softmax cross-entropy + ``dice_weight`` * mean per-class Dice loss for mutually
+    exclusive classes: ``pred`` is ``(N, C, D, H, W)`` logits (2 <= C <= 8), ``target`` the class map
+    ``(N, 1, D, H, W)`` or ``(N, D, H, W)``, fp32 or uint8, read by the kernel as it is.  A voxel
+    whose label is not an integer in [0, C) is ignored (``ignore_index`` for free, e.g. 255).
+    ``class_weights`` (C weights >= 0) are ``F.cross_entropy``'s ``weight``; the Dice mean leaves the
+    background class out unless ``include_background``; ``per_sample=True`` takes the Dice sums per
+    sample instead of over the batch.  ``classes.softmax_dice_ce_loss_host`` is the definition.
+
+    Two launches forward, one backward, no host sync, fixed-order sums (the same bits on every
+    run).  Under data parallelism the loss stays per replica."""
+
+    def __init__(self, ce_weight: float = 0.5, dice_weight: float = 0.5, smooth: float = 1.0, class_weights=None,
+                 include_background: bool = False, per_sample: bool = False):
+        super().__init__()
+        _validate_loss(ce_weight, dice_weight, smooth, class_weights)
+        self.ce_weight, self.dice_weight, self.smooth = ce_weight, dice_weight, smooth
+        self.class_weights = None if class_weights is None else tuple(float(w) for w in class_weights)
+        self.include_background, self.per_sample = bool(include_background), bool(per_sample)
+
+    def forward(self, pred, target):
+        return softmax_dice_ce_loss(pred, target, self.ce_weight, self.dice_weight, self.smooth, self.class_weights,
+                                    self.include_background, self.per_sample)
+
+
 # config["loss"] names of utils/trainer.py
 LOSSES = {"dice": DiceLoss, "bce_dice": BCEDiceLoss, "tversky": TverskyLoss, "focal_tversky": FocalTverskyLoss,
-          "focal": FocalLoss, "focal_tversky_focal": FocalTverskyFocalLoss}
+          "focal": FocalLoss, "focal_tversky_focal": FocalTverskyFocalLoss, "softmax_dice_ce": SoftmaxDiceCELoss}
 
 
 def create_criterion(loss="dice", loss_args=None):

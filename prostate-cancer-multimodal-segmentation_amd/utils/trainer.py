@@ -20,7 +20,11 @@ BatchNorm statistics and the global Dice stay per replica (plain BatchNorm3d, SU
 
 Config keys follow utils/trainer.py:40-49 (``device``, ``learning_rate``, ``batch_size``,
 ``num_epochs``, ``save_dir``, ``validation`` ...) plus ``loss`` ('dice' | 'bce_dice' | 'tversky' |
-'focal_tversky' | 'focal' | 'focal_tversky_focal' with ``loss_args``, or a module instance),
+'focal_tversky' | 'focal' | 'focal_tversky_focal' | 'softmax_dice_ce' with ``loss_args``, or a module
+instance), ``n_classes`` / ``class_values`` (default 1: the binary network and labels, untouched;
+``n_classes=C > 1``: C logit planes, the ``data_dir`` loaders keep the label a class map through
+``class_values`` -- see ``data.ProstateDataset`` -- for ``loss='softmax_dice_ce'``, and
+``validate_epoch`` also reports the mean foreground Dice of the argmax as ``last_val_dice``),
 ``precision`` ('bf16' | 'fp32'), ``checkpoint_decoder``, ``device_resample`` (the ``data_dir``
 loaders hand over the files' undecoded volumes and ``data.assemble_batch`` resamples them on
 the GPU, on the copy stream beside the previous step; same batches bit for bit), ``augment`` /
@@ -53,6 +57,7 @@ from typing import Iterable, Optional
 import torch
 import torch.distributed as dist
 
+from .. import classes
 from .._lib import call, query
 from ..amp import GradScaler
 from ..data import assemble_batch, device_batch, is_raw_batch
@@ -87,6 +92,7 @@ class BaseTrainer:
         self.scaler = GradScaler(init_scale=config.get("amp_init_scale", 2.0 ** 16)) if config.get("use_amp") else None
         self._clip_bufs = None
         self.last_grad_norm = None   # device tensor: the total gradient norm of the last clipped step
+        self.last_val_dice = self.last_val_class_dice = None   # n_classes > 1: set by validate_epoch
         self._resume = (float("inf"), 0)   # (best loss, patience) carried by a loaded checkpoint
         if self.distributed:
             self._broadcast_params()
@@ -95,7 +101,8 @@ class BaseTrainer:
 
     # ---- construction (utils/trainer.py:76-158) ----
     def _create_model(self):
-        return UNet3D(n_modalities=self.config.get("n_modalities", 5), n_classes=1,
+        return UNet3D(n_modalities=self.config.get("n_modalities", 5),
+                      n_classes=classes.check_n_classes(self.config.get("n_classes", 1)),
                       precision=self.config.get("precision", "bf16"),
                       checkpoint_decoder=self.config.get("checkpoint_decoder", False)).to(self.device)
 
@@ -136,7 +143,8 @@ class BaseTrainer:
                               # augment=None it cuts the same patches every epoch
                               patches=self.config.get("patches"),
                               # both loaders: the modalities are placed by their header geometry
-                              align=self.config.get("align"), corrections=self.config.get("corrections"))
+                              align=self.config.get("align"), corrections=self.config.get("corrections"),
+                              n_classes=self.config.get("n_classes", 1), class_values=self.config.get("class_values"))
 
     def _broadcast_params(self):
         eng = self.model.engine()
@@ -257,12 +265,22 @@ class BaseTrainer:
     def _validate_sums(self):
         self.model.eval()
         total, n = 0.0, 0
+        C = self.config.get("n_classes", 1)
+        # n_classes > 1: the validation set's (C, 3) class-overlap counts, on the device (zeros on a
+        # rank without a batch, so that every rank joins the all-reduce)
+        self._val_counts = torch.zeros((C, 3), dtype=torch.int64, device=self.device) if C > 1 else None
         with torch.no_grad():
             for batch in self.val_loader:
                 batch = device_batch(batch, self.device)
                 out = self.model(batch["image"].to(self.device))
-                total += self.criterion(out, batch["label"].to(self.device)).item()
+                labels = batch["label"].to(self.device)
+                total += self.criterion(out, labels).item()
                 n += 1
+                if C > 1:  # the argmax of every case against its class map (pcms_probs_to_labels, pcms_class_overlap)
+                    logits = out.float().contiguous()
+                    pred = torch.stack([classes.labels_on_grid_device(x, tuple(x.shape[1:]))[0] for x in logits])
+                    counts = classes.class_overlap_device(pred, labels.reshape(pred.shape).to(torch.uint8), C)
+                    self._val_counts += counts
         return total, n
 
     def validate_epoch(self):
@@ -270,7 +288,11 @@ class BaseTrainer:
         parallelism each rank evaluates whole batches of the single-process batching
         (data.get_dataloader, ``is_training=False``: batches r, r + W, ...; no padding) and
         the (sum, count) pair is summed over ranks, so every rank gets the full-set value the
-        single-process reference computes."""
+        single-process reference computes.
+        With ``n_classes > 1`` the epoch also leaves ``last_val_dice``: the mean over the
+        foreground classes of the Dice of the argmax class map against the labels, from the
+        class-overlap counts of the whole validation set (summed over ranks), and
+        ``last_val_class_dice``, the per-class list."""
         if self.val_loader is None:
             return None
         total, n = self._validate_sums()
@@ -278,6 +300,11 @@ class BaseTrainer:
             t = torch.tensor([total, float(n)], dtype=torch.float64, device=self.model.engine().flat_p.device)
             dist.all_reduce(t)
             total, n = float(t[0]), int(t[1])
+        if self._val_counts is not None:
+            if self.distributed:
+                dist.all_reduce(self._val_counts)
+            dice, _ = classes.scores_of_counts(self._val_counts.cpu().numpy())
+            self.last_val_class_dice, self.last_val_dice = dice, sum(dice[1:]) / max(len(dice) - 1, 1)
         return total / max(n, 1)
 
     def save_checkpoint(self, epoch, loss, is_best=False, best_loss=None, patience=None,
